@@ -3,6 +3,13 @@
 Gaussian rasterizer at 1080p with 1M synthetic Gaussians (BASELINE.json
 config 2), and the 1 -> 8 GPU data-parallel curve (config 5).
 
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up,
+times the K steps, writes the last step's outputs with ``--dump-outputs DIR``
+(dump_outputs) and prints one JSON line with ``value`` and ``ms_per_step``.
+Everything else described below -- sub-results, CPU baselines, per-stage
+timing, rooflines, workload statistics, the other exchange and the
+collectives alone, config 3's other legs -- runs only with ``--full``.
+
 N = 1 (default): one *step* = one forward + backward through the drop-in API
 (``diff_gaussian_rasterization.GaussianRasterizer``, autograd) of one
 1920x1080 view of the 1M-Gaussian scene with a fixed N(0,1) cotangent
@@ -61,6 +68,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # had been SLP-packed.)
 VALU_PEAK_WAVE_INSTR_PER_S = 256 * 4 * 2.4e9 / 2.4
 METRIC = "rendered views/sec (fwd+bwd) at 1080p, 1M Gaussians; achieved HBM GB/s %"
+AMR_METRIC = "foveated AMR frames/sec (forward-only render(), 5 fovea steps) at 1080p, 1M Gaussians"
 
 CONFIGS = {
     # name: P, W, H, tile size, kind
@@ -449,6 +457,44 @@ def cpu_amr_test_path(seed: int = 0):
             "seconds": sec}
 
 
+# ---------------------------------------------------------- output dump ---
+DUMP_BUDGET_BYTES = 60_000_000  # (the dump stays under 64 MB)
+
+
+def dump_outputs(out_dir: str, arrays: dict, seed: int) -> None:
+    """--dump-outputs: write the arrays the timed path returned in its last
+    step as <out_dir>/<name>.npy (float32; integer outputs such as radii are
+    converted), at most DUMP_BUDGET_BYTES in all, so two builds can be compared
+    output for output.  The budget is shared smallest array first: an array
+    within its share is written whole; a larger one as a sample of its
+    flattened elements at sorted indices drawn from default_rng(seed) (with
+    the array's position among the sorted names), the same indices in every
+    run with the same arguments.  manifest.json lists each array's full shape
+    and how many elements were kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: t for n, t in arrays.items() if t is not None}
+    names = sorted(arrays)
+    order = sorted(names, key=lambda n: (arrays[n].numel(), n))
+    left, manifest = DUMP_BUDGET_BYTES, {}
+    for i, n in enumerate(order):
+        t = arrays[n].detach()
+        keep = min(t.numel(), left // (len(order) - i) // 4)
+        flat = t.reshape(-1)
+        if keep < t.numel():
+            import torch
+            idx = np.sort(np.random.default_rng([seed, names.index(n)]).integers(0, t.numel(), keep))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy()
+        if keep == t.numel():
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+        left -= a.nbytes
+        manifest[n] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "kept": int(keep),
+                       "sampled": keep < t.numel()}
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump({"seed": seed, "arrays": manifest}, f, indent=1)
+
+
 # --------------------------------------------------------------- context ---
 class Ctx:
     def __init__(self, world, rank, local_rank, distributed, dev, args):
@@ -566,8 +612,9 @@ def stage_table(prof: dict, steps: int, P, ws, views=1, key: dict | None = None)
 
 
 # --------------------------------------------------------- config 2 / 4 ---
-def run_fwd_bwd(cfg_name: str, ctx: Ctx, steps: int, warmup: int) -> dict:
-    """One view forward + backward through the drop-in autograd API per step."""
+def run_fwd_bwd(cfg_name: str, ctx: Ctx, steps: int, warmup: int, dump: str | None = None) -> dict:
+    """One view forward + backward through the drop-in autograd API per step.
+    `dump`: directory for the last timed step's outputs (dump_outputs)."""
     import torch
     from diff_gaussian_rasterization import GaussianRasterizer
     from gaussian_splatting_with_eye_tracking_amd import _C
@@ -589,6 +636,8 @@ def run_fwd_bwd(cfg_name: str, ctx: Ctx, steps: int, warmup: int) -> dict:
                                    shs=params["shs"], scales=params["scales"], rotations=params["rotations"])
         torch.autograd.backward(color, dpix)
 
+        return color, _radii
+
     ramp = settle(step, warmup, ctx)
     # Inside the timed region only the roofline kernel (render_bwd, the
     # dominant stage at configs 2 and 4) records its event pair: each timed
@@ -602,10 +651,15 @@ def run_fwd_bwd(cfg_name: str, ctx: Ctx, steps: int, warmup: int) -> dict:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     ctx.barrier()
     elapsed = time.perf_counter() - t0
+    if dump and ctx.rank == 0:
+        # what the caller of the timed step holds after the last one
+        dump_outputs(dump, dict({"color": last[0], "radii": last[1], "grad_means2D": means2D.grad},
+                                **{"grad_" + k: p.grad for k, p in params.items()}), ctx.args.seed)
+    del last
     prof_timed, prof = {}, {}
     if not ctx.args.no_profile:
         prof_timed = _C.profile_read(True)
@@ -618,7 +672,7 @@ def run_fwd_bwd(cfg_name: str, ctx: Ctx, steps: int, warmup: int) -> dict:
     (elapsed,) = ctx.max_over_ranks(elapsed)
     res = {"value": ctx.world * steps / elapsed, "unit": "views/s", "ms_per_step": 1000.0 * elapsed / steps,
            "ramp_steps": ramp}
-    if ctx.rank != 0:
+    if ctx.rank != 0 or not ctx.args.full:
         return res
     ws = workload_stats(settings, params, P, W, H)
     stages = stage_table(prof, steps, P, ws, key=config_key(P, W, H, 16))
@@ -656,10 +710,13 @@ def views_of_rank(global_views: int, world: int, rank: int):
     return list(range(rank * vl, (rank + 1) * vl)), yaws
 
 
-def run_multiview(ctx: Ctx, steps: int, warmup: int, global_views: int, exchange_alt: bool = True) -> dict:
+def run_multiview(ctx: Ctx, steps: int, warmup: int, global_views: int, exchange_alt: bool = True,
+                  dump: str | None = None) -> dict:
     """a fixed global batch of `global_views` yawed views per
     step, global_views / N per rank; every rank ends the step with the summed
-    parameter gradients of all views."""
+    parameter gradients of all views.  `exchange_alt` and the collectives
+    timed alone run under --full only.  `dump`: directory for the last timed
+    step's outputs (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from diff_gaussian_rasterization import GaussianRasterizer
@@ -724,14 +781,20 @@ def run_multiview(ctx: Ctx, steps: int, warmup: int, global_views: int, exchange
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(k):
-            fn()
+            last = fn()
         torch.cuda.synchronize()
         ctx.barrier()
         (el,) = ctx.max_over_ranks(time.perf_counter() - t0)
+        timed.last = last
         return el
 
     ramp = settle(step_views, warmup, ctx)
     el_views = timed(step_views, steps)
+    if dump and ctx.rank == 0:
+        # the step's result: the parameter gradients summed over all views
+        dump_outputs(dump, dict(zip(("grad_means3D", "grad_shs", "grad_opacities", "grad_scales",
+                                     "grad_rotations"), timed.last)), ctx.args.seed)
+    timed.last = None
     prof = {}
     if not ctx.args.no_profile:
         # (per-stage events on one stream: concurrent views would time each
@@ -746,6 +809,8 @@ def run_multiview(ctx: Ctx, steps: int, warmup: int, global_views: int, exchange
         vs["n"] = n_streams
     res = {"value": G * steps / el_views, "unit": "views/s", "ms_per_step": 1000.0 * el_views / steps,
            "ramp_steps": ramp, "view_streams": vs["n"]}
+    if not ctx.args.full:
+        return res
     extra = {}
     if exchange_alt:
         for _ in range(max(1, warmup // 2)):
@@ -817,12 +882,16 @@ def amr_algorithmic_bytes(ranges: np.ndarray, levels: np.ndarray) -> float:
     return float((L * (40.0 * n + 20.0 * 256)).sum())
 
 
-def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
+def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True, dump: str | None = None) -> dict:
     """Config 3: forward-only foveated rendering (gaussian_renderer_amr's
     render(): foveaStep 0..4 through _RasterizeGaussians, summing the step
     images -- rasterization_amr.render_steps, the sums fused into the steps;
     and render_once(): foveaStep -2 with interpolation).  Per-frame and
-    single-GPU: for N > 1 every rank renders its own frames (replicas only)."""
+    single-GPU: for N > 1 every rank renders its own frames (replicas only).
+    A plain run times the 5-step frame alone; render_once, the apply chain,
+    the per-stage and per-step passes and the extension legs run under
+    --full.  `dump`: directory for the last timed frame's outputs
+    (dump_outputs)."""
     import torch
     from diff_gaussian_rasterization_amr import GaussianRasterizer, _RasterizeGaussians
     from gaussian_splatting_with_eye_tracking_amd import _C
@@ -856,7 +925,7 @@ def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
             ev[0].record()
         acc, _radii, gb, bb, ib = RA.render_steps(*a, st, fused=fused, enders=ev[1:] if record else None,
                                                   after_step0=lv)
-        return acc, gb, bb, ib
+        return acc, _radii, gb, bb, ib
 
     rast = GaussianRasterizer(st)
 
@@ -869,15 +938,24 @@ def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
         frame_once()
 
     with torch.no_grad():
-        ramp = settle(warm_pair, warmup, ctx)
+        # (a plain run warms only the frame it times)
+        ramp = settle(warm_pair if ctx.args.full else frame_5step, warmup, ctx)
         ctx.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            frame_5step()
+            last = frame_5step()
         torch.cuda.synchronize()
         ctx.barrier()
         el5 = time.perf_counter() - t0
+        if dump and ctx.rank == 0:
+            # what render_steps' caller receives: the summed frame and step 0's radii
+            dump_outputs(dump, {"color": last[0], "radii": last[1]}, ctx.args.seed)
+        del last
+        if not ctx.args.full:
+            (el5,) = ctx.max_over_ranks(el5)
+            return {"value": ctx.world * steps / el5, "unit": "frames/s", "ms_per_step": 1000.0 * el5 / steps,
+                    "ramp_steps": ramp, "metric": AMR_METRIC}
         # (--no-profile, the rocprofv3 runs: only the timed frame's launches, so
         # the kernel statistics are the frame's -- no apply-chain or per-step
         # passes launching the step kernel one step at a time)
@@ -960,7 +1038,7 @@ def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
     if ctx.rank != 0:
         return res
     with torch.no_grad():
-        acc, gb, bb, ib = frame_5step()
+        acc, _r, gb, bb, ib = frame_5step()
         torch.cuda.synchronize()
         K = int(_C.parse_buffers(gb, bb, ib, P, 0, W, H, 32)["hdr"][0].item())
         d = _C.parse_buffers(gb, bb, ib, P, K, W, H, 32)
@@ -969,7 +1047,7 @@ def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
         V3 = int((_RasterizeGaussians.apply(*a, 0, e, u8, u8, u8, False, st)[1] > 0).sum().item())
         fovea_hist = None
         if extensions:
-            _, _, _, ibf = frame_5step(fovea=True)
+            _, _, _, _, ibf = frame_5step(fovea=True)
             lvf = _C.parse_buffers(gb, bb, ibf, P, K, W, H, 32)["levels"].cpu().numpy().astype(np.int64)
             fovea_hist = np.bincount(lvf, minlength=5)[1:].tolist()
     stages = {n: {"avg_ms": ms / cnt, "launches": cnt, "ms_per_frame": ms / steps} for n, (ms, cnt) in prof.items()
@@ -983,7 +1061,7 @@ def run_amr(ctx: Ctx, steps: int, warmup: int, extensions: bool = True) -> dict:
                                  per=stages["amr_render"]["launches"] / steps, stream_read=0.0)
         roofline["per"] = "frame (the one amr_render launch of steps 1..4; traffic per frame)"
     res.update({
-        "metric": "foveated AMR frames/sec (forward-only render(), 5 fovea steps) at 1080p, 1M Gaussians",
+        "metric": AMR_METRIC,
         "config": {"workload": f"cfg3_amr_1080p_1M: {P} Gaussians, {W}x{H}, 32x32 AMR tiles, 5-step foveated "
                                f"render() per frame" + (", replicas" if ctx.world > 1 else ""),
                    "P": P, "width": W, "height": H, "K_instances": K, "parallelism": f"replicas{ctx.world}",
@@ -1028,14 +1106,23 @@ def parse_args(argv=None):
                     help="after the W warmup steps, untimed steps for about this long so the GPU clocks "
                          "have settled before the timed region (0: off); the count is in the line as ramp_steps")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="N = 1: skip the config 3 / 4 / 5 sub-results")
-    ap.add_argument("--no-profile", action="store_true", help="disable the per-stage event timing")
-    ap.add_argument("--no-ext", action="store_true", help="config 3: skip the extension legs (fovea discs, "
-                    "AMR backward), e.g. for PMC passes")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-stage event timing and rooflines, workload "
+                         "statistics, the config 3 / 4 / 5 sub-results, the other exchanges and legs of configs 3 "
+                         "and 5, the CPU baselines (each can be dropped again with the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sub", action="store_true", help="--full, N = 1: skip the config 3 / 4 / 5 sub-results")
+    ap.add_argument("--no-profile", action="store_true", help="--full: disable the per-stage event timing")
+    ap.add_argument("--no-ext", action="store_true", help="--full, config 3: skip the extension legs (fovea discs, "
+                    "AMR backward)")
     ap.add_argument("--launcher-dry-run", action="store_true",
                     help="test hook: rendezvous over gloo on the CPU and print the JSON skeleton (no GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_sub = args.no_profile = args.no_ext = True
+    return args
 
 
 def dry_run(world, rank, global_views: int = 8):
@@ -1132,17 +1219,18 @@ def main(argv=None):
     ctx = Ctx(world, rank, local_rank, distributed, dev, args)
     cfg = args.config or ("cfg2_1080p_1M" if world == 1 else "cfg5_8view_1080p_1M")
     kind = CONFIGS[cfg]["kind"]
-    base = {"metric": METRIC, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "higher_is_better": True, "vs_baseline": None, "dtype": "fp32",
+    base = {"metric": METRIC, "workload": cfg, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full, "higher_is_better": True, "vs_baseline": None, "dtype": "fp32",
             "data": "synthetic (SURVEY §8(d) generator, seed 0)"}
+    dump = args.dump_outputs
     if kind == "amr":
-        r = run_amr(ctx, args.steps, args.warmup, extensions=not args.no_ext)
+        r = run_amr(ctx, args.steps, args.warmup, extensions=not args.no_ext, dump=dump)
         out = dict(base, **r, scaling="weak")
     elif kind == "multiview":
-        r = run_multiview(ctx, args.steps, args.warmup, args.views)
+        r = run_multiview(ctx, args.steps, args.warmup, args.views, dump=dump)
         out = dict(base, **r, scaling="strong" if world > 1 else "weak")
     else:
-        r = run_fwd_bwd(cfg, ctx, args.steps, args.warmup)
+        r = run_fwd_bwd(cfg, ctx, args.steps, args.warmup, dump=dump)
         out = dict(base, **r, scaling="weak")
     if rank == 0 and world == 1 and kind == "fwd_bwd" and cfg == "cfg2_1080p_1M" and not args.no_sub:
         torch.cuda.empty_cache()

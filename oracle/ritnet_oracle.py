@@ -9,10 +9,10 @@ the reference's shapes (32 channels, 1 input, 4 classes) for GPU parity
 tests that must not depend on the reference's checkpoint.
 
 Pinning: tests/test_eye_tracking_host.py runs this restatement with the
-reference's own checkpoint (RITnet/best_model.pkl, loaded weights_only) on
-the reference's eye.png through eye_tracking.preprocess and compares the
-labels with the prediction the reference saved (eye_seg_pred.png, right
-half) -- in this container only, where /root/reference exists.
+reference's own checkpoint (RITnet/best_model.pkl; its tensors are stored
+in tests/golden/ritnet_weights by tools/make_eye_golden.py) on the
+reference's eye.png through eye_tracking.preprocess and compares the labels
+with the prediction the reference saved (eye_seg_pred.png, right half).
 """
 from __future__ import annotations
 

@@ -2,6 +2,10 @@
 and tolerance checks with the tolerances of BASELINE.json's north_star."""
 from __future__ import annotations
 
+import glob
+import io
+import os
+
 import numpy as np
 
 from gaussian_splatting_with_eye_tracking_amd import synthetic as S
@@ -9,6 +13,63 @@ from gaussian_splatting_with_eye_tracking_amd import synthetic as S
 # north_star: image L1 < 1e-5, gradients within 1e-4 relative.
 IMAGE_L1_TOL = 1e-5
 GRAD_REL_TOL = 1e-4
+
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLDEN_PART_BYTES = 900_000  # a committed file stays under 1 MiB
+
+
+def _npz_bytes(**arrays) -> int:
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    return buf.getbuffer().nbytes
+
+
+def save_golden(stem: str, arrays: dict) -> list:
+    """Write `arrays` as tests/golden/<stem>.npz, or, where that file would
+    exceed GOLDEN_PART_BYTES, as <stem>.part0.npz, .part1.npz, ...: whole
+    arrays are packed into parts in order; an array too large for one part is
+    cut along axis 0 into pieces "name@0", "name@1", ... (load_golden joins
+    them).  Returns the files written."""
+    items = []
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        n = -(-_npz_bytes(**{k: v}) // GOLDEN_PART_BYTES)
+        while n > 1 and any(_npz_bytes(p=p) > GOLDEN_PART_BYTES for p in np.array_split(v, n)):
+            n += 1
+        items += [(k, v)] if n == 1 else [(f"{k}@{i}", p) for i, p in enumerate(np.array_split(v, n))]
+    parts, cur = [], {}
+    for k, v in items:
+        if cur and _npz_bytes(**cur, **{k: v}) > GOLDEN_PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = v
+    parts.append(cur)
+    names = [f"{stem}.npz"] if len(parts) == 1 else [f"{stem}.part{i}.npz" for i in range(len(parts))]
+    for stale in glob.glob(os.path.join(GOLDEN_DIR, f"{stem}.npz")) + glob.glob(
+            os.path.join(GOLDEN_DIR, f"{stem}.part*.npz")):
+        os.remove(stale)
+    for name, part in zip(names, parts):
+        np.savez_compressed(os.path.join(GOLDEN_DIR, name), **part)
+    return names
+
+
+def load_golden(stem: str) -> dict:
+    """The arrays save_golden(stem, ...) wrote, whole again."""
+    one = os.path.join(GOLDEN_DIR, f"{stem}.npz")
+    files = [one] if os.path.exists(one) else sorted(
+        glob.glob(os.path.join(GOLDEN_DIR, f"{stem}.part*.npz")),
+        key=lambda f: int(f.rsplit(".part", 1)[1][:-len(".npz")]))
+    assert files, f"no golden fixture {stem}"
+    raw = {}
+    for f in files:
+        with np.load(f) as d:
+            raw.update({k: d[k] for k in d.files})
+    out = {k: v for k, v in raw.items() if "@" not in k}
+    for k in sorted({k.split("@")[0] for k in raw if "@" in k}):
+        n = sum(1 for r in raw if r.startswith(k + "@"))
+        out[k] = np.concatenate([raw[f"{k}@{i}"] for i in range(n)])
+    return out
 
 
 def scene_and_camera(P: int, W: int, H: int, seed: int = 0, **kw):

@@ -50,3 +50,45 @@ def test_bench_single_rank_dry_run():
                        capture_output=True, text=True, env=_env(), timeout=100)
     assert r.returncode == 0, r.stderr
     assert json.loads(r.stdout.strip().splitlines()[-1])["n_gpus"] == 1
+
+
+def test_plain_run_drops_everything_but_the_headline():
+    """Without --full every extra leg is off; --full turns them on, and each
+    --no-* option takes its leg out again."""
+    import bench
+    legs = ("no_cpu_baseline", "no_sub", "no_profile", "no_ext")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 2 and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in legs)
+    full = bench.parse_args(["--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    part = bench.parse_args(["--full", "--no-sub"])
+    assert part.no_sub and not part.no_profile
+
+
+def test_dump_outputs_is_repeatable_and_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; arrays within their share of the
+    budget whole, larger ones as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 300)
+    g = torch.Generator().manual_seed(1)
+    arrays = {"color": torch.rand(3, 20, 30, generator=g), "radii": torch.arange(50, dtype=torch.int32),
+              "grad_shs": torch.rand(100, 16, 3, generator=g), "unset": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, seed=0)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("color", "radii", "grad_shs")}
+    assert not (tmp_path / "a" / "unset.npy").exists()
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 4 * 300
+    np.testing.assert_array_equal(got["radii"], np.arange(50, dtype=np.float32))  # within its share: whole
+    assert got["color"].shape == (125,) and got["grad_shs"].shape == (125,)       # (300 - 50) / 2 each
+    for n, a in got.items():
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / f"{n}.npy"))
+    man = json.load(open(tmp_path / "a" / "manifest.json"))["arrays"]
+    assert man["grad_shs"] == {"shape": [100, 16, 3], "dtype": "float32", "kept": 125, "sampled": True}
+    # the sample holds elements of the array at the recorded seed's indices
+    idx = np.sort(np.random.default_rng([0, sorted(got).index("grad_shs")]).integers(0, 4800, 125))
+    np.testing.assert_array_equal(got["grad_shs"], arrays["grad_shs"].reshape(-1).numpy()[idx])

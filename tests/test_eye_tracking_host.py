@@ -6,8 +6,8 @@
   reproduce the segmentation the reference saved (eye_seg_pred.png, decoded
   into tests/golden/eye_pins.npz by tools/make_eye_golden.py) -- this pins
   both the preprocessing and the network restatement to the reference's own
-  output.  It needs /root/reference (the checkpoint is not copied into this
-  repository) and is skipped elsewhere.
+  output.  The checkpoint's tensors are stored in tests/golden/ritnet_weights
+  (tools/make_eye_golden.py).
 * Preprocessing pins and properties that need no reference.
 * The fovea mapping of SURVEY §8(d) config 3.
 """
@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 
 import ritnet_oracle as R
+from gs_helpers import load_golden
 
-REF = "/root/reference"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eye_pins.npz")
 
 
@@ -27,14 +27,12 @@ def _E():
     return E
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "RITnet", "best_model.pkl")),
-                    reason="needs the reference's RITnet checkpoint (this container only)")
 @pytest.mark.timeout(600)
 def test_oracle_with_reference_checkpoint_reproduces_saved_prediction():
     import torch
     E = _E()
     g = np.load(GOLD)
-    sd = torch.load(os.path.join(REF, "RITnet", "best_model.pkl"), map_location="cpu", weights_only=True)
+    sd = {k: torch.from_numpy(v) for k, v in load_golden("ritnet_weights").items()}
     lab = R.labels(R.forward(sd, E.preprocess(g["eye"])))
     assert lab.shape == g["labels"].shape == (640, 400)
     agree = float((lab == g["labels"]).mean())

@@ -5,7 +5,8 @@
   utils/graphics_utils.py:getProjectionMatrix / getWorld2View2 /
   geom_transform_points) -- and directly against /root/reference when it is
   mounted (this container; not the GPU box);
-* against its own committed regression vectors G1-G4 (bit-exact);
+* against its own committed regression vectors G1-G4 (bit-exact; the larger
+  ones are stored in parts of under 1 MiB, gs_helpers.load_golden);
 * against hand-computed known answers of the CUDA-only stages (the
   reference has no tests for those: SURVEY §4).
 """
@@ -17,6 +18,7 @@ import pytest
 
 import oracle as O
 from gaussian_splatting_with_eye_tracking_amd import synthetic as S
+from gs_helpers import load_golden
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 REF = "/root/reference"
@@ -110,7 +112,7 @@ def _regen_inputs(d):
 
 @pytest.mark.parametrize("name", ["G1", "G2"])
 def test_oracle_regression_base(name):
-    d = np.load(os.path.join(GOLD, f"oracle_{name}.npz"))
+    d = load_golden(f"oracle_{name}")
     cam, sc, dpix = _regen_inputs(d)
     s = O.settings_from_camera(cam, bg=(0.1, 0.2, 0.3))
     kw = dict(shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
@@ -125,7 +127,7 @@ def test_oracle_regression_base(name):
 
 
 def test_oracle_regression_amr():
-    d = np.load(os.path.join(GOLD, "oracle_G3.npz"))
+    d = load_golden("oracle_G3")
     cam = S.make_camera(256, 256)
     sc = S.make_scene(10000, cam, seed=0)
     s = O.settings_from_camera(cam)
@@ -140,7 +142,7 @@ def test_oracle_regression_amr():
 
 
 def test_oracle_regression_knn():
-    d = np.load(os.path.join(GOLD, "oracle_G4.npz"))
+    d = load_golden("oracle_G4")
     dist, morton, idx, boxes = O.knn_intermediates(d["points"])
     np.testing.assert_array_equal(dist, d["dist"])
     np.testing.assert_array_equal(morton, d["morton_sorted"])

@@ -27,8 +27,8 @@ cfg_of() { case "$1" in *2) echo cfg2_1080p_1M;; *3) echo cfg3_amr_1080p_1M;; *4
 for step in "$@"; do
   case "$step" in
     probe) run probe 60 bash -c 'echo "cpu.max: $(cat /sys/fs/cgroup/cpu.max 2>&1)"; echo "cfs: $(cat /sys/fs/cgroup/cpu/cpu.cfs_quota_us 2>&1) / $(cat /sys/fs/cgroup/cpu/cpu.cfs_period_us 2>&1)"; echo "nproc $(nproc) OMP_NUM_THREADS=${OMP_NUM_THREADS:-unset}"; python3 -c "import bench; print(bench.cpu_share())"' ;;
-    gaptrace) run gaptrace 600 rocprofv3 --kernel-trace -d "$O/gaptrace" -o run --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sub ;;
-    benchns) run bench_ns 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sub ;;
+    gaptrace) run gaptrace 600 rocprofv3 --kernel-trace -d "$O/gaptrace" -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sub ;;
+    benchns) run bench_ns 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sub ;;
     ab) run "ab_${AB_NAME:-x}" 600 python tools/ab_tuning.py $AB_ARGS ;;
     ab2) run "ab_${AB_NAME:-x}_2" 600 python tools/ab_tuning.py $AB_ARGS2 ;;
     pytestk) run "pytest_${PT_NAME:-k}" 900 python -u -m pytest tests -x -v -m gpu -p no:cacheprovider --timeout 300 --timeout-method thread -rf -k "$PT_K" ;;
@@ -37,17 +37,17 @@ for step in "$@"; do
     amrtests) run pytest_amr 900 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_parity_configs.py tests/test_gpu_cull.py -v -m gpu -p no:cacheprovider --timeout 600 --timeout-method thread -rf -k "amr or config3 or cull" ;;
     parity) run pytest_parity 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_cull.py -q -m gpu -p no:cacheprovider --timeout 300 -rf ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 5 ;;
-    benchdef) run bench_default 600 python bench.py ;;  # the driver's exact command
-    bench3) run bench_cfg3 600 python bench.py --config cfg3_amr_1080p_1M --steps 20 --warmup 3 ;;
-    bench4) run bench_cfg4 600 python bench.py --config cfg4_bicycle_6M --steps 10 --warmup 3 --no-cpu-baseline ;;
-    dist2) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 ;;
-    dist2l) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2_launcher 600 python bench.py --gpus 2 --steps 5 --warmup 2 ;;
-    dist2amr) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2amr 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 5 --warmup 2 --config cfg3_amr_1080p_1M ;;
-    benchnp) run bench_np 400 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-profile &&
-             run bench_p 400 python bench.py --steps 50 --warmup 5 --no-cpu-baseline ;;
-    benchq) run bench 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
-    prof) run rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile ;;
+    bench) run bench 600 python bench.py --full --steps 20 --warmup 5 ;;
+    benchdef) run bench_default 600 python bench.py --full ;;  # every leg at the default 50 steps, 10 warm-up
+    bench3) run bench_cfg3 600 python bench.py --full --config cfg3_amr_1080p_1M --steps 20 --warmup 3 ;;
+    bench4) run bench_cfg4 600 python bench.py --full --config cfg4_bicycle_6M --steps 10 --warmup 3 --no-cpu-baseline ;;
+    dist2) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 ;;
+    dist2l) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2_launcher 600 python bench.py --full --gpus 2 --steps 5 --warmup 2 ;;
+    dist2amr) GS_BENCH_SHARE_DEVICE=1 GS_BENCH_BACKEND=gloo run bench_dist2amr 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 2 --steps 5 --warmup 2 --config cfg3_amr_1080p_1M ;;
+    benchnp) run bench_np 400 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-profile &&
+             run bench_p 400 python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline ;;
+    benchq) run bench 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ;;
+    prof) run rocprof 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-profile ;;
     pmc_issue2) run pmc_issue2 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d gpurun_out/pmc_issue2 -o run --output-format csv -- python3 bench.py --config cfg2_1080p_1M --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-sub --no-ext ;;
     pmc_issue4) run pmc_issue4 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --kernel-trace -d gpurun_out/pmc_issue4 -o run --output-format csv -- python3 bench.py --config cfg4_bicycle_6M --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-sub --no-ext ;;
     mv) run pytest_mv 400 python -m pytest tests/test_gpu_multiview.py tests/test_gpu_dist_views.py -q -m gpu -p no:cacheprovider --timeout 300 -rf &&
@@ -64,8 +64,8 @@ for step in "$@"; do
       run "pmc_${c}_fetch" 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "gpurun_out/pmc_${c}_fetch" -o run --output-format csv -- python3 bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-sub --no-ext &&
       run "pmc_${c}_write" 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "gpurun_out/pmc_${c}_write" -o run --output-format csv -- python3 bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-sub --no-ext &&
       run "pmc_${c}_valu" 300 rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace -d "gpurun_out/pmc_${c}_valu" -o run --output-format csv -- python3 bench.py --config "$c" --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-sub --no-ext ;;
-    gaptrace3) run gaptrace3 600 rocprofv3 --kernel-trace -d "$O/gaptrace3" -o run --output-format csv -- python3 bench.py --config cfg3_amr_1080p_1M --steps 20 --warmup 3 --no-cpu-baseline --no-ext ;;
-    bench5) run bench_cfg5 600 python bench.py --config cfg5_8view_1080p_1M --steps 10 --warmup 3 --no-cpu-baseline ;;
+    gaptrace3) run gaptrace3 600 rocprofv3 --kernel-trace -d "$O/gaptrace3" -o run --output-format csv -- python3 bench.py --full --config cfg3_amr_1080p_1M --steps 20 --warmup 3 --no-cpu-baseline --no-ext ;;
+    bench5) run bench_cfg5 600 python bench.py --full --config cfg5_8view_1080p_1M --steps 10 --warmup 3 --no-cpu-baseline ;;
     trace3) run trace_cfg3 300 rocprofv3 --kernel-trace -d gpurun_out/trace_cfg3 -o run --output-format csv -- python3 bench.py --config cfg3_amr_1080p_1M --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-ext ;;
     sqa2|sqa3|sqa4|sqa5|sqb2|sqb3|sqb4|sqb5)  # SQ issue / wait counters per kernel (two 8-counter sets)
       c=$(cfg_of "$step")

@@ -11,6 +11,11 @@ reads the reference):
              network's (transposed) orientation;
 * label_gt : eye_label_gt.npy, uint8 [400, 640] (ground truth);
 * clahe    : eye_tracking.clahe(apply_gamma(eye)) from this build (regression pin).
+
+And tests/golden/ritnet_weights[.partN].npz: the tensors of the reference's
+RITnet checkpoint (RITnet/best_model.pkl, a state dict), one array per entry,
+so the test that pins the network restatement to the saved prediction needs
+nothing outside the repository.
 """
 import os
 import sys
@@ -43,6 +48,11 @@ def main():
     out = os.path.join(ROOT, "tests", "golden", "eye_pins.npz")
     np.savez_compressed(out, eye=eye, labels=labels, label_gt=gt, clahe=E.clahe(E.apply_gamma(eye)))
     print("wrote", out, os.path.getsize(out), "bytes")
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from gs_helpers import save_golden
+    sd = torch.load(os.path.join(REF, "RITnet", "best_model.pkl"), map_location="cpu", weights_only=True)
+    print("wrote", save_golden("ritnet_weights", {k: v.numpy() for k, v in sd.items()}))
 
 
 if __name__ == "__main__":
