@@ -36,10 +36,10 @@ def _load_native():
 _C = _load_native()
 
 from .rasterization import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: E402
-                            rasterize_gaussians, _RasterizeGaussians)
+                            rasterize_gaussians, _RasterizeGaussians, set_deterministic)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_C", "native_library_paths"]
+           "_C", "native_library_paths", "set_deterministic"]
 
 
 def native_library_paths() -> list[str]:

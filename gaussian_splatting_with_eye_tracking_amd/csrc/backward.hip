@@ -39,6 +39,7 @@
 namespace gsamd {
 
 constexpr int kNG = 9;      // gradient terms per (pixel, Gaussian)
+static_assert(kDetRow == kNG, "the deterministic backward's partial rows hold the nine terms");
 constexpr int kAccRow = 9;   // LDS accumulator row (floats; odd stride: 9 scalar stores per row)
 constexpr int kPPL = 4;      // pixels per lane: one wave64 covers the 16x16 tile (gs_blend.cuh mapping)
 
@@ -48,7 +49,15 @@ constexpr int kPPL = 4;      // pixels per lane: one wave64 covers the 16x16 til
 // and the flush fused into the staging reduce (below).  !kSel (the fallback,
 // and the AMR backward): the predicate form, full sums by transposition into
 // LDS rows, one 64-B atomic row per (tile, Gaussian) at the end of each batch.
-template <bool kSel, bool kAMR = false, bool kOpT = false>
+// kDet (the deterministic backward, on the fallback form): grad_accum is the
+// caller's partials array [R][kNG] instead -- the flush stores the nine terms
+// of sorted instance i (= range.x + its index in the tile's list) at row i
+// with plain stores and issues no atomic; reduce_partials_kernel (below) sums
+// each Gaussian's rows in a fixed order.  Every row below min(n,
+// max_contrib[tile]) is written (zeros where the default flush adds nothing),
+// the rows at or past it are never read.
+// (a template parameter, as kAMR: run-time branches cost the base kernel 12 %)
+template <bool kSel, bool kAMR = false, bool kOpT = false, bool kDet = false>
 __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     int W, int H, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ max_contrib,
     const uint32_t* __restrict__ point_list, const float2* __restrict__ means2D,
@@ -59,6 +68,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     const uint32_t* __restrict__ hdr) {
 #pragma clang fp contract(fast)
     static_assert(!(kSel && kAMR), "the AMR backward is the fallback form");
+    static_assert(!kDet || (!kSel && !kAMR), "the deterministic backward is the base fallback form");
     constexpr int kB = 64;  // Gaussians per LDS batch
     __shared__ uint32_t s_id[2][kB];  // double-buffered: the next batch's ids land while this one flushes
     // (x, y, r, g) and the scaled conic / opacity as two b128 reads, b as one
@@ -201,6 +211,13 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     }
     // = max_contrib[tile] for a whole base tile; AMR: no per-tile max_contrib
     // was recorded for the sub-lattice, the wave max is the block's
+    if constexpr (kDet) {
+        // rows [wave max, min(n, max_contrib)) -- none when max_contrib is this
+        // forward's -- are read by the reduction and visited by no batch: zeros
+        const int mw = min(m, __builtin_amdgcn_readfirstlane((int)wave_last));
+        float* part = grad_accum + (size_t)range.x * kNG;
+        for (int i = mw * kNG + lane; i < m * kNG; i += 64) part[i] = 0.f;
+    }
     m = min(kAMR ? n : m, __builtin_amdgcn_readfirstlane((int)wave_last));
     if (m == 0) return;
     // Row masks: the forward's exact hit codes when it left them (gs_blend.cuh
@@ -566,7 +583,14 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
 #pragma unroll 4
             for (int i = 0; i < kB / 4; i++) {
                 const int r = (tid >> 4) + 4 * i;
-                const bool live = r < cnt && comp < kNG && ((written >> (r & 63)) & 1ull);
+                const bool wr = (written >> (r & 63)) & 1ull;
+                if constexpr (kDet) {
+                    // a row no pixel took stores zeros: every row the reduction
+                    // reads is written by this call
+                    if (r < cnt && comp < kNG && !wr)
+                        grad_accum[(size_t)(range.x + (uint32_t)(top - 1 - r)) * kNG + comp] = 0.f;
+                }
+                const bool live = r < cnt && comp < kNG && wr;
                 if (live) {
                     // row sums (c0, c1, c2, s0, sx, sy, sxx, sxy, syy) -> the
                     // reference's nine terms: v = ka * row[ia] + kb * sy, with o and
@@ -582,7 +606,8 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
                                    : (comp >= 5 && comp <= 7) ? -0.5f * o : 1.0f;
                     const float kb = comp == 3 ? -o * cy * ddelx_dx : comp == 4 ? -o * cz * ddely_dy : 0.0f;
                     const float v = ka * qa + kb * qb;
-                    if (v != 0.f) atomicAdd(&grad_accum[(size_t)s_id[par][r] * kGradRow + comp], v);
+                    if constexpr (kDet) grad_accum[(size_t)(range.x + (uint32_t)(top - 1 - r)) * kNG + comp] = v;
+                    else if (v != 0.f) atomicAdd(&grad_accum[(size_t)s_id[par][r] * kGradRow + comp], v);
                 }
             }
         }
@@ -632,6 +657,112 @@ void launch_render_backward(int W, int H, const ImageView& img, const BinningVie
     if (g_bwd_variant == 0) GS_BWD_LAUNCH(false);
     else GS_BWD_LAUNCH(true, false, true);
 #undef GS_BWD_LAUNCH
+}
+
+// The deterministic backward's second pass: grad_accum[p][0..8] of every
+// visible Gaussian = the sum of its partial rows (render_bwd_kernel kDet)
+// over the tiles of its rectangle in ascending tile index, accumulated in
+// float64 and rounded to float32 once, stored with a plain store -- the same
+// bits whatever order the blend's workgroups ran in.
+// It reads only what the backward is promised (point_list, the image and the
+// geometry buffer): the Gaussian's row in a tile is found by binary search of
+// the tile's list, which is sorted by (depth bits, Gaussian index) ascending
+// -- the duplicate's key -- so the search is exact.  A rectangle whose area
+// is not tiles_touched[p], or a tile whose list does not hold the Gaussian
+// (buffers that are not one forward's), raises through the header word
+// kHdrError and stores NaNs in the Gaussian's row: never a stale partial.
+// Rows at or past min(n, max_contrib[tile]) are skipped, as the blend skips
+// them.
+// Work split: 16 lanes per Gaussian.  Each lane searches one tile of the
+// rectangle (the ~log2 n dependent gathers of up to 16 tiles in flight at
+// once), then lanes 0..8 read the found rows' nine values, one 36-B run per
+// row, 16 rows' loads issued ahead of the float64 adds; rectangles of more
+// than 16 tiles take further rounds.  (One thread per Gaussian was not built:
+// it serialises the searches of a rectangle, reads each row as nine 4-B
+// gathers at a 36-B stride, and a wave then lasts as long as its largest
+// rectangle; most Gaussians touch 1-4 tiles, a few 80 and more.  One wave per
+// Gaussian would idle 48+ lanes at the median.)
+// Measured at config 2 (K = 4.44M instances, kernel trace,
+// profiles/r07_deterministic_kernel_stats.csv): this kernel 0.734 ms, the
+// kDet blend 0.411 ms (the default select-form blend 0.316 ms): the ~10 search
+// steps of two dependent gathers each per instance are the cost, not the row
+// reads.  Not built: the direct-slot layout (rows at a per-Gaussian offset +
+// the tile's ordinal in the rectangle, no search) -- it needs an offset table,
+// a zero-fill of the rows the blend's cut skips, and the rectangle in the
+// blend's flush.
+constexpr uint32_t kDetNone = 0xffffffffu;  // no row: the tile's entry is past the blend's cut, or the lane has no tile
+__global__ void __launch_bounds__(256) reduce_partials_kernel(
+    int P, uint32_t R, uint32_t gx, uint32_t gy, const int* __restrict__ radii, const float2* __restrict__ means2D,
+    const float* __restrict__ depths, const uint32_t* __restrict__ tiles_touched, const uint32_t* __restrict__ ranges,
+    const uint32_t* __restrict__ max_contrib, const uint32_t* __restrict__ point_list,
+    const float* __restrict__ partials, float* __restrict__ grad_accum, uint32_t* __restrict__ hdr,
+    uint32_t err_token) {
+    const int p = (int)((blockIdx.x * 256u + threadIdx.x) >> 4);
+    const int sub = threadIdx.x & 15;
+    if (p >= P) return;  // (whole 16-lane groups)
+    const int rad = radii[p];
+    if (rad <= 0) return;
+    const float2 xy = means2D[p];
+    const Rect r = get_rect(xy.x, xy.y, rad, 16, 16, gx, gy);
+    const uint32_t w = r.x1 - r.x0;
+    const uint32_t area = w * (r.y1 - r.y0);
+    const uint64_t key = ((uint64_t)float_bits(depths[p]) << 32) | (uint32_t)p;
+    bool bad = area != tiles_touched[p];
+    double acc = 0.0;
+    if (!bad) {
+        for (uint32_t i0 = 0; i0 < area; i0 += 16) {  // row-major over the rectangle: ascending tile index
+            uint32_t pos = kDetNone;
+            const uint32_t i = i0 + (uint32_t)sub;
+            if (i < area) {
+                const uint32_t tile = (r.y0 + i / w) * gx + r.x0 + i % w;
+                const uint2 range = reinterpret_cast<const uint2*>(ranges)[tile];
+                const uint32_t end = min(range.y, R), beg = min(range.x, end);
+                uint32_t lo = beg, hi = end;
+                while (lo < hi) {  // lower bound of key in the tile's list
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    const uint32_t id = point_list[mid];
+                    const uint64_t k = ((uint64_t)float_bits(depths[min(id, (uint32_t)(P - 1))]) << 32) | id;
+                    if (k < key) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < end && point_list[lo] == (uint32_t)p) {
+                    if (lo - beg < min(end - beg, max_contrib[tile])) pos = lo;
+                } else {
+                    bad = true;
+                }
+            }
+            float v[16];
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const uint32_t q = (uint32_t)__shfl((int)pos, t, 16);
+                v[t] = (q != kDetNone && sub < kNG) ? partials[(size_t)q * kNG + sub] : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < 16; t++) acc += (double)v[t];
+        }
+    }
+    // the group's verdict: its 16 bits of the wave's ballot
+    const uint64_t any_bad = __ballot(bad);
+    const bool gbad = ((any_bad >> (threadIdx.x & 48u)) & 0xffffull) != 0ull;
+    if (sub < kNG) grad_accum[(size_t)p * kGradRow + sub] = gbad ? __uint_as_float(0x7fc00000u) : (float)acc;
+    if (gbad && sub == 0) hdr[kHdrError] = err_token;
+}
+
+void launch_render_backward_deterministic(int W, int H, int P, int R, const ImageView& img, const BinningView& b,
+                                          const GeomView& g, const int* radii, const float* colors, const float* bg,
+                                          const float* dL_dpix, float* partials, uint32_t err_token, hipStream_t s) {
+    const int gx = (W + 15) / 16, gy = (H + 15) / 16;
+    if (gx == 0 || gy == 0 || P <= 0 || R <= 0) return;
+    // the partials array in grad_accum's place (kDet); the forward's work
+    // buckets still order the launch, heaviest tiles first
+    hipLaunchKernelGGL((render_bwd_kernel<false, false, false, true>), dim3(gx * gy), dim3(64), 0, s, W, H, img.ranges,
+                       img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
+                       reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
+                       dL_dpix, bg, partials, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr);
+    const unsigned groups = ((unsigned)P + 15u) / 16u;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(groups), dim3(256), 0, s, P, (uint32_t)R, (uint32_t)gx,
+                       (uint32_t)gy, radii, reinterpret_cast<const float2*>(g.means2D), g.depths, g.tiles_touched,
+                       img.ranges, img.max_contrib, b.point_list, partials, g.grad_accum, g.hdr, err_token);
 }
 
 // The foveated (AMR) blend backward: 32-px tile ranges, one wave per

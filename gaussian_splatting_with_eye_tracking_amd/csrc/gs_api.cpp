@@ -602,6 +602,57 @@ int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image
 }
 
 namespace {
+// The deterministic backward's scratch: one row of kDetRow floats per sorted
+// instance (gs_backward_deterministic_scratch_bytes).
+size_t det_scratch_bytes(int R) { return R > 0 ? align_up(sizeof(float) * kDetRow * (size_t)R) : 0; }
+
+struct DetScratch {
+    bool on = false;
+    char* base = nullptr;
+    size_t bytes = 0;
+};
+
+// Nothing is launched when the scratch cannot hold the call's partial rows.
+void check_det_scratch(const DetScratch& d, int R, const char* who) {
+    if (!d.on || R <= 0) return;
+    if (!d.base) throw GsError(std::string(who) + ": scratch is NULL (gs_backward_deterministic_scratch_bytes)");
+    if (d.bytes < det_scratch_bytes(R))
+        throw GsError(std::string(who) + ": scratch of " + std::to_string(d.bytes) + " bytes, " +
+                      std::to_string(det_scratch_bytes(R)) + " needed (gs_backward_deterministic_scratch_bytes)");
+}
+
+// The blend backward into g.grad_accum: the default (float atomics onto the
+// zeroed rows) or the deterministic one (partial rows + fixed-order sums,
+// plain stores onto every visible Gaussian's row: no zeroing needed, but the
+// rows are no longer the forward's clean zeros, so the flag is taken).
+void blend_backward(const DetScratch& det, int width, int height, int P, int R, const ImageView& img,
+                    const BinningView& b, const GeomView& g, const int* radii, const float* colors,
+                    const float* background, const float* dL_dpix, int debug, hipStream_t s) {
+    if (!det.on || R <= 0 || P <= 0) {
+        zero_accum_unless_clean(g, P, s);
+        if (R > 0 && P > 0) {
+            StageTimer _t(kRenderBwd, s, true);
+            launch_render_backward(width, height, img, b, g, colors, background, dL_dpix, s, R);
+        }
+        return;
+    }
+    take_accum_clean(g.grad_accum);
+    const uint32_t token = next_error_token();
+    {
+        StageTimer _t(kRenderBwd, s);
+        launch_render_backward_deterministic(width, height, P, R, img, b, g, radii, colors, background, dL_dpix,
+                                             reinterpret_cast<float*>(det.base), token, s);
+    }
+    if (debug) {  // (debug calls synchronise after every stage: the reduction's verdict is read here)
+        stage_check(true, s, "render_backward");
+        uint32_t err = 0;
+        GS_HIP(hipMemcpy(&err, g.hdr + kHdrError, sizeof(err), hipMemcpyDeviceToHost));
+        if (err == token)
+            throw GsError("deterministic backward: the geometry / binning / image buffers are not one forward's "
+                          "(a Gaussian's tile rectangle and the sorted tile lists disagree)");
+    }
+}
+
 // Shared by the base and the AMR backward.  amr_mode 0: base 16-px tiles;
 // != 0: AMR 32-px tiles, the rendered sub-lattices of foveaStep amr_mode
 // (> 0) or of render_once (< 0; dL_dpix already folded through the
@@ -614,8 +665,9 @@ int rasterizer_backward_impl(int amr_mode, int P, int D, int M, int R, const flo
                              char* binning_buffer, char* img_buffer, const float* dL_dpix, float* dL_dmean2D,
                              float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                              float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
-                             hipStream_t s) {
+                             hipStream_t s, const DetScratch& det = DetScratch{}) {
     {
+        check_det_scratch(det, R, "gs_rasterizer_backward_deterministic");
         if (P <= 0) return 0;
         const int tile = amr_mode != 0 ? 32 : 16;
         const int T = ((width + tile - 1) / tile) * ((height + tile - 1) / tile);
@@ -626,12 +678,15 @@ int rasterizer_backward_impl(int amr_mode, int P, int D, int M, int R, const flo
         carve_image(img_buffer, (size_t)width * height, T, &img, tile);
         carve_binning(binning_buffer, R, &b);
         if (!radii) radii = g.radii;
-        zero_accum_unless_clean(g, P, s);
         const float* colors = colors_precomp ? colors_precomp : g.rgb;
-        if (R > 0) {
-            StageTimer _t(kRenderBwd, s, amr_mode == 0);
-            if (amr_mode != 0) launch_amr_render_backward(width, height, amr_mode, img, b, g, colors, background, dL_dpix, s);
-            else launch_render_backward(width, height, img, b, g, colors, background, dL_dpix, s, R);
+        if (amr_mode != 0) {
+            zero_accum_unless_clean(g, P, s);
+            if (R > 0) {
+                StageTimer _t(kRenderBwd, s);
+                launch_amr_render_backward(width, height, amr_mode, img, b, g, colors, background, dL_dpix, s);
+            }
+        } else {
+            blend_backward(det, width, height, P, R, img, b, g, radii, colors, background, dL_dpix, debug, s);
         }
         stage_check(debug != 0, s, "render_backward");
         BackwardGaussArgs a;
@@ -723,13 +778,43 @@ int gs_amr_rasterizer_backward(int P, int D, int M, int R, const float* backgrou
     });
 }
 
-int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int width, int height,
-                                      const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
-                                      const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                                      char* geom_buffer, char* binning_buffer, char* img_buffer,
-                                      const float* dL_dpix, float* out_record, int debug, void* stream) {
+size_t gs_backward_deterministic_scratch_bytes(int P, int R) {
+    (void)P;  // (the reduction finds each Gaussian's rows by search: no per-Gaussian index)
+    return det_scratch_bytes(R);
+}
+
+int gs_rasterizer_backward_deterministic(int P, int D, int M, int R, const float* background, int width, int height,
+                                         const float* means3D, const float* shs, const float* colors_precomp,
+                                         const float* scales, float scale_modifier, const float* rotations,
+                                         const float* cov3D_precomp, const float* viewmatrix,
+                                         const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                         const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                         const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                         float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch,
+                                         size_t scratch_bytes, int debug, void* stream) {
     return guarded([&]() -> int {
-        if (P < 0) throw GsError("gs_rasterizer_backward_view_grads: negative P");
+        DetScratch det;
+        det.on = true;
+        det.base = scratch;
+        det.bytes = scratch_bytes;
+        return rasterizer_backward_impl(0, P, D, M, R, background, width, height, means3D, shs, colors_precomp,
+                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
+                                        dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
+                                        dL_dsh, dL_dscale, dL_drot, debug, static_cast<hipStream_t>(stream), det);
+    });
+}
+
+namespace {
+int backward_view_grads_impl(int P, int R, const float* background, int width, int height,
+                             const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
+                             const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                             char* geom_buffer, char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                             float* out_record, int debug, void* stream, const DetScratch& det, const char* who) {
+    {
+        if (P < 0) throw GsError(std::string(who) + ": negative P");
+        check_det_scratch(det, R, who);
         hipStream_t s = static_cast<hipStream_t>(stream);
         const int tile = 16;
         const int T = ((width + tile - 1) / tile) * ((height + tile - 1) / tile);
@@ -740,14 +825,46 @@ int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int
         carve_image(img_buffer, (size_t)width * height, T, &img, tile);
         carve_binning(binning_buffer, R, &b);
         if (!radii) radii = g.radii;
-        zero_accum_unless_clean(g, P, s);
         const float* colors = colors_precomp ? colors_precomp : g.rgb;
-        if (R > 0 && P > 0) { StageTimer _t(kRenderBwd, s, true); launch_render_backward(width, height, img, b, g, colors, background, dL_dpix, s, R); }
+        blend_backward(det, width, height, P, R, img, b, g, radii, colors, background, dL_dpix, debug, s);
         stage_check(debug != 0, s, "render_backward");
         launch_pack_view_grads(P, g, radii, colors_precomp == nullptr, viewmatrix, projmatrix, campos, width, height,
                                tan_fovx, tan_fovy, out_record, s);
         stage_check(debug != 0, s, "pack_view_grads");
         return 0;
+    }
+}
+}  // namespace
+
+int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int width, int height,
+                                      const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
+                                      const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                      char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                      const float* dL_dpix, float* out_record, int debug, void* stream) {
+    return guarded([&]() -> int {
+        return backward_view_grads_impl(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
+                                        dL_dpix, out_record, debug, stream, DetScratch{},
+                                        "gs_rasterizer_backward_view_grads");
+    });
+}
+
+int gs_rasterizer_backward_view_grads_deterministic(int P, int R, const float* background, int width, int height,
+                                                    const float* colors_precomp, const float* viewmatrix,
+                                                    const float* projmatrix, const float* campos, float tan_fovx,
+                                                    float tan_fovy, const int* radii, char* geom_buffer,
+                                                    char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                                                    float* out_record, char* scratch, size_t scratch_bytes,
+                                                    int debug, void* stream) {
+    return guarded([&]() -> int {
+        DetScratch det;
+        det.on = true;
+        det.base = scratch;
+        det.bytes = scratch_bytes;
+        return backward_view_grads_impl(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
+                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
+                                        dL_dpix, out_record, debug, stream, det,
+                                        "gs_rasterizer_backward_view_grads_deterministic");
     });
 }
 

@@ -114,6 +114,17 @@ void set_ritnet_mfma(int v);
 // Blend backward (base/cr/backward.cu:399-557) into g.grad_accum.
 void launch_render_backward(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                             const float* colors, const float* bg, const float* dL_dpix, hipStream_t s, int K);
+// The same in a fixed summation order (gs_rasterizer_backward_deterministic):
+// the blend stores one row of kDetRow floats per sorted instance into
+// `partials` ([R][kDetRow], plain stores, no atomics), then a reduction sums
+// each visible Gaussian's rows over its tiles in ascending tile index, in
+// float64, rounds once and stores grad_accum[p][0..8].  A geometry / image /
+// binning triple that is not one forward's stores err_token in the header's
+// error word (and NaNs in the rows it concerns).
+constexpr int kDetRow = 9;
+void launch_render_backward_deterministic(int W, int H, int P, int R, const ImageView& img, const BinningView& b,
+                                          const GeomView& g, const int* radii, const float* colors, const float* bg,
+                                          const float* dL_dpix, float* partials, uint32_t err_token, hipStream_t s);
 
 struct BackwardGaussArgs {
     int P, D, M;

@@ -307,6 +307,17 @@ Tensor AmrAccumulateStep(const Tensor& background, const Tensor& colors_in, int 
 // base/rasterize_points.cu:117-196
 using Grads8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
+// set_deterministic_backward: this thread's base backward bindings
+// (rasterize_gaussians_backward, _lean, _view_grads) call the deterministic C
+// entries, with the scratch from torch's allocator on the current stream.
+// Persistent until set again; the Python wrappers set it around their call.
+thread_local bool t_det_backward = false;
+
+Tensor det_scratch(int P, int R, const Tensor& like) {
+    const size_t n = gs_backward_deterministic_scratch_bytes(P, R);
+    return torch::empty({(int64_t)n}, like.options().dtype(torch::kByte));
+}
+
 // amr_step 0: the base backward; != 0: the AMR (foveated) backward of
 // foveaStep amr_step (< 0: render_once, with `interpolate`).
 Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, const Tensor& means3D_in,
@@ -354,7 +365,19 @@ Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, co
         for (const Tensor* bt : {&geomBuffer, &binningBuffer, &imageBuffer})
             require_like(*bt, means3D, "geometry / binning / image buffer", -1, torch::kByte);
         int rc;
-        if (amr_step == 0) {
+        if (amr_step == 0 && t_det_backward) {
+            Tensor scratch = det_scratch(P, R, means3D);
+            rc = gs_rasterizer_backward_deterministic(
+                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
+                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
+                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
+                fptr(dL_dout), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
+                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
+                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
+                fptr_mut(dL_drotations), scratch.numel() ? reinterpret_cast<char*>(scratch.data_ptr()) : nullptr,
+                (size_t)scratch.numel(), debug, stream_of(means3D));
+        } else if (amr_step == 0) {
             rc = gs_rasterizer_backward(
                 P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
                 fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
@@ -422,6 +445,9 @@ Grads8 AmrRasterizeGaussiansBackward(const Tensor& background, const Tensor& mea
                                      const Tensor& binningBuffer, const Tensor& imageBuffer, const int foveaStep,
                                      const bool interpolate_image, const bool debug) {
     TORCH_CHECK(foveaStep != 0, "foveaStep 0 renders nothing: its gradient is zero");
+    // (the AMR blend backward keeps its float atomics: raises, or warns, under
+    // torch.use_deterministic_algorithms, as torch's own such ops do)
+    if (t_det_backward) at::globalContext().alertNotDeterministic("amr_rasterize_gaussians_backward");
     return BackwardImpl(foveaStep, interpolate_image, background, means3D, radii, colors, scales, rotations,
                         scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                         degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, true);
@@ -455,6 +481,18 @@ Tensor RasterizeGaussiansBackwardViewGrads(const Tensor& background, const Tenso
         require_like(*bt, dL_dout, "geometry / binning / image buffer", -1, torch::kByte);
     TORCH_CHECK(radii.is_cuda() && radii.scalar_type() == torch::kInt32, "radii must be an int32 device tensor");
     require_like(radii, dL_dout, "radii", P, torch::kInt32);
+    if (t_det_backward) {
+        Tensor scratch = det_scratch(P, R, dL_dout);
+        check(gs_rasterizer_backward_view_grads_deterministic(
+                  P, R, fptr(bg), W, H, fptr(colors), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
+                  tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                  reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
+                  fptr(dL_dout), rec.data_ptr<float>(),
+                  scratch.numel() ? reinterpret_cast<char*>(scratch.data_ptr()) : nullptr, (size_t)scratch.numel(),
+                  debug, stream_of(dL_dout)),
+              "rasterize_gaussians_backward_view_grads");
+        return rec;
+    }
     check(gs_rasterizer_backward_view_grads(
               P, R, fptr(bg), W, H, fptr(colors), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
               tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
@@ -939,6 +977,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
     m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
     m.def("amr_rasterize_gaussians_backward", &AmrRasterizeGaussiansBackward);
+    m.def("set_deterministic_backward", [](bool on) { t_det_backward = on; });
+    m.def("get_deterministic_backward", []() { return t_det_backward; });
+    m.def("backward_deterministic_scratch_bytes",
+          [](int P, int R) { return gs_backward_deterministic_scratch_bytes(P, R); });
     m.def("mark_visible", &MarkVisible);
     m.def("rasterize_gaussians_backward_view_grads", &RasterizeGaussiansBackwardViewGrads);
     m.def("backward_gaussians_multiview", &BackwardGaussiansMultiview);

@@ -66,6 +66,46 @@ def _clear_hint(hinted: bool) -> None:
         _C.set_thread_option("fwd_no_grad", 0)
 
 
+# Deterministic backward (INTEGRATION.md "Deterministic backward"): None
+# follows torch.are_deterministic_algorithms_enabled() at each backward.
+_deterministic = None
+
+
+def set_deterministic(mode) -> None:
+    """Choose the blend backward's summation: ``True`` -- the fixed-order one
+    (ascending tile index, float64, one rounding: bit-reproducible), ``False``
+    -- the default float atomics, ``None`` (the default) -- whatever
+    ``torch.are_deterministic_algorithms_enabled()`` says when a backward
+    runs.  The autograd wrappers apply the choice around their native call;
+    ``True`` / ``False`` also set the calling thread's native flag
+    (``_C.set_deterministic_backward``), which direct users of the ``_C``
+    backward bindings -- ``training.py``'s native sequence -- run under
+    (``None`` clears it).  The AMR backward has no deterministic form."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise ValueError(f"set_deterministic: mode must be None, True or False, not {mode!r}")
+    _deterministic = mode
+    _C.set_deterministic_backward(bool(mode))
+
+
+def deterministic_requested() -> bool:
+    """What a backward that starts now runs as (set_deterministic)."""
+    return torch.are_deterministic_algorithms_enabled() if _deterministic is None else _deterministic
+
+
+class _DeterministicScope:
+    """The calling thread's native flag set to the requested mode for one
+    native call, and put back afterwards."""
+
+    def __enter__(self):
+        self.prev = _C.get_deterministic_backward()
+        _C.set_deterministic_backward(deterministic_requested())
+
+    def __exit__(self, *exc):
+        _C.set_deterministic_backward(self.prev)
+        return False
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @classmethod
     def apply(cls, *args):
@@ -103,9 +143,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, sh, s.sh_degree, s.campos,
                 geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations) = _call(_C.rasterize_gaussians_backward_lean, args, s.debug,
-                                              "snapshot_bw.dump", "backward")
+        with _DeterministicScope():
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+             grad_scales, grad_rotations) = _call(_C.rasterize_gaussians_backward_lean, args, s.debug,
+                                                  "snapshot_bw.dump", "backward")
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None)
 

@@ -37,6 +37,7 @@ import torch.nn as nn
 
 from . import _C
 from .rasterization import GaussianRasterizationSettings, _check_exactly_one, _clear_hint, _hint_forward_only, _or_empty  # noqa: F401
+from .rasterization import _DeterministicScope, set_deterministic  # noqa: F401
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -112,11 +113,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         s = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations) = _C.amr_rasterize_gaussians_backward(
-            s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_color, sh, s.sh_degree, s.campos, geomBuffer,
-            ctx.num_rendered, binningBuffer, imgBuffer, step, ctx.interpolate, s.debug)
+        # (the AMR blend backward keeps its float atomics: with determinism
+        # requested the binding raises -- or warns, warn_only -- under
+        # torch.use_deterministic_algorithms, as torch's own such ops do)
+        with _DeterministicScope():
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+             grad_scales, grad_rotations) = _C.amr_rasterize_gaussians_backward(
+                s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_color, sh, s.sh_degree, s.campos, geomBuffer,
+                ctx.num_rendered, binningBuffer, imgBuffer, step, ctx.interpolate, s.debug)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp) + nones
 

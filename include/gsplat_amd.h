@@ -102,6 +102,56 @@ int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int
                                       char* geom_buffer, char* binning_buffer, char* img_buffer,
                                       const float* dL_dpix, float* out_record, int debug, void* stream);
 
+/* The deterministic backward (no reference counterpart: the reference's
+ * blend backward adds with float atomics in arrival order,
+ * base/cr/backward.cu:518-545, as gs_rasterizer_backward does).
+ *
+ * gs_rasterizer_backward_deterministic and
+ * gs_rasterizer_backward_view_grads_deterministic take the arguments of
+ * their namesakes plus a caller-owned device scratch, and compute the same
+ * gradients with a fixed summation order, which is the contract: the blend
+ * stores the nine terms of every sorted (tile, Gaussian) instance as a row
+ * of the scratch (plain stores, no atomics), then each visible Gaussian's
+ * rows are summed over the tiles of its rectangle in ASCENDING TILE INDEX
+ * (row-major), accumulated in FLOAT64 and ROUNDED TO FLOAT32 ONCE.  Two
+ * calls on the same forward buffers and cotangent, or on two forwards of the
+ * same inputs, return the same bits, whatever the tunings and the launch
+ * order.  Everything after the blend is element-wise and shared with the
+ * default entries.
+ *
+ * scratch: at least gs_backward_deterministic_scratch_bytes(P, R) bytes,
+ * 256-B aligned = 36 R bytes rounded up to 256 (0 for R <= 0; P is reserved).
+ * Its contents need no initialisation and are not preserved: every row the
+ * sums read is written by the same call.  With R > 0, a NULL or too small
+ * scratch returns a negative value (gs_last_error() says how many bytes are
+ * needed) and launches nothing: the outputs are untouched.
+ *
+ * Asynchronous on `stream`, no host synchronisation, no allocation (debug !=
+ * 0 synchronises after every stage, as everywhere).  P == 0 / R == 0 as the
+ * default entries: every output element written (zeros).  Deterministic and
+ * default calls may follow each other on one forward in any order.  The
+ * buffers must be one base forward's: a geometry / binning / image triple
+ * that disagrees stores NaNs in the gradients it concerns (and raises under
+ * debug).  The AMR backward has no deterministic form. */
+size_t gs_backward_deterministic_scratch_bytes(int P, int R);
+int gs_rasterizer_backward_deterministic(int P, int D, int M, int R, const float* background, int width, int height,
+                                         const float* means3D, const float* shs, const float* colors_precomp,
+                                         const float* scales, float scale_modifier, const float* rotations,
+                                         const float* cov3D_precomp, const float* viewmatrix,
+                                         const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                         const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                         const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                                         float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                         float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch,
+                                         size_t scratch_bytes, int debug, void* stream);
+int gs_rasterizer_backward_view_grads_deterministic(int P, int R, const float* background, int width, int height,
+                                                    const float* colors_precomp, const float* viewmatrix,
+                                                    const float* projmatrix, const float* campos, float tan_fovx,
+                                                    float tan_fovy, const int* radii, char* geom_buffer,
+                                                    char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                                                    float* out_record, char* scratch, size_t scratch_bytes,
+                                                    int debug, void* stream);
+
 /* Stage 2: the per-Gaussian backward (base/cr/backward.cu:20-396) of V views
  * at once, summed over the views in view order; views = V stage-1 records
  * back to back (device).  Writes every element of dL_dmeans3D[P][3],
