@@ -381,6 +381,11 @@ struct ForwardIn {
     int width, height;
     float scale_modifier, tan_fovx, tan_fovy;
     int prefiltered;
+    // this call's options (forward_in: the thread options, the one-shots consumed)
+    bool store_drgb;      // sh_drgb, and not under the forward-only hint
+    bool store_cov3d;
+    bool fwd_zero;        // fwd_zero, and not under the forward-only hint
+    bool step0_unfilled;  // AMR forwards only
 };
 
 // Per-call token for the header's error word (never 0: a zeroed header at
@@ -402,18 +407,32 @@ uint32_t next_error_token() {
 // backward would fall back to the SH coefficients).  One-shot: every forward
 // entry consumes it.
 thread_local int t_fwd_no_grad = 0;
-bool take_fwd_no_grad() {
-    const bool v = t_fwd_no_grad != 0;
-    t_fwd_no_grad = 0;
-    return v;
-}
-thread_local bool t_store_drgb = true;  // this forward's choice (take_fwd_no_grad)
 // gs_set_thread_option("amr_step0_unfilled", 1): one-shot -- the NEXT AMR
 // forward on this thread, if at foveaStep 0, leaves its image unwritten: the
 // caller overwrites every pixel (gs_amr_accumulate_step with
 // GSPLAT_AMD_AMR_STEPS_1_TO_4_FILL), so step 0's 3 x H x W zero fill is skipped.
 // Every AMR forward entry consumes it.
 thread_local int t_amr_step0_unfilled = 0;
+
+// A forward entry's arguments plus this thread's options: the only reader of
+// the thread options, and where the one-shots are consumed.  Called before
+// `guarded`, so a call that returns early (P <= 0) or throws consumes them too.
+ForwardIn forward_in(bool amr, int P, int D, int M, const float* background, int width, int height,
+                     const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                     const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                     const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                     float tan_fovy, int prefiltered) {
+    ForwardIn in{P, D, M, background, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                 viewmatrix, projmatrix, cam_pos, width, height, scale_modifier, tan_fovx, tan_fovy, prefiltered};
+    const bool grad = t_fwd_no_grad == 0;
+    t_fwd_no_grad = 0;
+    in.store_drgb = t_sh_drgb != 0 && grad;
+    in.store_cov3d = t_store_cov3d != 0;
+    in.fwd_zero = t_fwd_zero != 0 && grad;
+    in.step0_unfilled = amr && t_amr_step0_unfilled != 0;
+    if (amr) t_amr_step0_unfilled = 0;
+    return in;
+}
 
 PreprocessArgs make_pp(const ForwardIn& in, int tile) {
     PreprocessArgs a;
@@ -440,8 +459,8 @@ PreprocessArgs make_pp(const ForwardIn& in, int tile) {
     a.focal_x = (float)in.width / (2.0f * in.tan_fovx);
     a.block = tile;
     a.prefiltered = in.prefiltered;
-    a.store_cov3d = t_store_cov3d;
-    a.store_drgb = t_sh_drgb && t_store_drgb;
+    a.store_cov3d = in.store_cov3d;
+    a.store_drgb = in.store_drgb;
     a.zero_words = nullptr;
     a.zero_n = 0;
     a.err_token = 0;
@@ -458,6 +477,48 @@ struct Binned {
     int* radii;
 };
 
+int tile_count(int W, int H, int tile) { return ((W + tile - 1) / tile) * ((H + tile - 1) / tile); }
+
+// The image buffer alone as a view (where no geometry or binning buffer is involved).
+ImageView image_view(char* image, int W, int H, int tile) {
+    ImageView v;
+    carve_image(image, (size_t)W * H, tile_count(W, H, tile), &v, tile);
+    return v;
+}
+
+// The geometry / binning / image buffers a caller hands back after a forward,
+// as views (gs_layout.h): P, W x H and the tile size fix the geometry and the
+// image view, K the binning view (`amr`: with the AMR extension).  A null
+// buffer gives null views; radii are the geometry buffer's own.
+Binned carve_buffers(char* geom, char* binning, char* image, int P, int K, int W, int H, int tile,
+                     bool amr = false) {
+    Binned r{};
+    r.K = K;
+    r.T = tile_count(W, H, tile);
+    carve_geom(geom, P, &r.g);
+    r.img = image_view(image, W, H, tile);
+    carve_binning(binning, K, &r.b, amr ? &r.ab : nullptr);
+    r.radii = r.g.radii;
+    return r;
+}
+
+// K of the buffers of an earlier forward: the caller's hint, else read back
+// from the geometry header, synchronously (the reference reads K back here,
+// amr/cr/rasterizer_impl.cu:337-340).  K > 0 without a binning buffer is
+// refused with `missing`.
+int rendered_count(int hint, char* geom, int P, const char* binning, hipStream_t s, const char* missing) {
+    int K = hint;
+    if (K < 0) {
+        GeomView g;
+        carve_geom(geom, P, &g);
+        uint32_t hdr[4];
+        read_header(g.hdr, hdr, s);
+        K = (int)hdr[kHdrNumRendered];
+    }
+    if (K > 0 && !binning) throw GsError(missing);
+    return K;
+}
+
 // preprocess -> tile scan -> (K read-back) -> duplicate -> per-tile sort.
 // `before_k`: work that needs the scan but not K, enqueued behind the K copy
 // and run while the host waits for it.
@@ -470,7 +531,7 @@ Binned preprocess_and_bin(const ForwardIn& in, const gs_buffer& geometry, const 
     r.T = gx * gy;
     const size_t N = (size_t)W * H;
     // the optional tail (gs_layout.h) only when this forward writes into it
-    const bool tail = t_store_cov3d || (in.colors_precomp == nullptr && t_sh_drgb && t_store_drgb);
+    const bool tail = in.store_cov3d || (in.colors_precomp == nullptr && in.store_drgb);
     char* gbase = call_resize(geometry, carve_geom(nullptr, in.P, nullptr, tail, tile == 32), "geometry");
     carve_geom(gbase, in.P, &r.g);
     set_accum_clean(r.g.grad_accum, false);  // this forward decides afresh
@@ -576,12 +637,12 @@ int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image
                           float scale_modifier, const float* rotations, const float* cov3D_precomp,
                           const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                           float tan_fovy, int prefiltered, float* out_color, int* radii, int debug, void* stream) {
-    t_store_drgb = !take_fwd_no_grad();
+    const ForwardIn in = forward_in(false, P, D, M, background, width, height, means3D, shs, colors_precomp, opacities,
+                                    scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                    tan_fovx, tan_fovy, prefiltered);
     return guarded([&]() -> int {
         if (P <= 0) return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
-        ForwardIn in{P, D, M, background, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                     viewmatrix, projmatrix, cam_pos, width, height, scale_modifier, tan_fovx, tan_fovy, prefiltered};
         Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
         const float* feats = colors_precomp ? colors_precomp : r.g.rgb;
         bool zeroed;
@@ -590,7 +651,7 @@ int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image
             // the accumulator rows are zeroed behind the blend only when a
             // backward can follow (not under the forward-only hint: a later
             // backward of this forward then zeroes them itself)
-            const bool zero = t_fwd_zero && t_store_drgb;
+            const bool zero = in.fwd_zero;
             zeroed = launch_render_forward(width, height, r.img, r.b, r.g, feats, background, out_color, s,
                                            zero ? r.g.grad_accum : nullptr, zero ? (size_t)kGradRow * (size_t)P : 0,
                                            reinterpret_cast<uint8_t*>(r.b.scratch));
@@ -620,6 +681,24 @@ void check_det_scratch(const DetScratch& d, int R, const char* who) {
         throw GsError(std::string(who) + ": scratch of " + std::to_string(d.bytes) + " bytes, " +
                       std::to_string(det_scratch_bytes(R)) + " needed (gs_backward_deterministic_scratch_bytes)");
 }
+
+// One backward call's arguments, filled by its C entry; what a form does not
+// take stays null (the view-grads forms: of `a` only P, radii and the camera,
+// plus out_record; the others: no out_record).
+struct BackwardCall {
+    // P, D, M, the per-Gaussian inputs, the camera and the nine outputs, as the
+    // per-Gaussian kernel takes them.  Its other members (cov3D,
+    // has_cov_precomp, the focal lengths, drgb, hdr; radii when null) are not
+    // the caller's: rasterizer_backward_impl sets them on its own copy.
+    BackwardGaussArgs a{};
+    int R = 0, width = 0, height = 0;
+    const float *background = nullptr, *colors_precomp = nullptr, *cov3D_precomp = nullptr, *dL_dpix = nullptr;
+    char *geom_buffer = nullptr, *binning_buffer = nullptr, *img_buffer = nullptr;
+    float* out_record = nullptr;
+    DetScratch det;
+    int debug = 0;
+    hipStream_t s = nullptr;
+};
 
 // The blend backward into g.grad_accum: the default (float atomics onto the
 // zeroed rows) or the deterministic one (partial rows + fixed-order sums,
@@ -657,73 +736,117 @@ void blend_backward(const DetScratch& det, int width, int height, int P, int R, 
 // != 0: AMR 32-px tiles, the rendered sub-lattices of foveaStep amr_mode
 // (> 0) or of render_once (< 0; dL_dpix already folded through the
 // interpolation when it was applied).
-int rasterizer_backward_impl(int amr_mode, int P, int D, int M, int R, const float* background, int width,
-                             int height, const float* means3D, const float* shs, const float* colors_precomp,
-                             const float* scales, float scale_modifier, const float* rotations,
-                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                             const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
-                             char* binning_buffer, char* img_buffer, const float* dL_dpix, float* dL_dmean2D,
-                             float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
-                             float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
-                             hipStream_t s, const DetScratch& det = DetScratch{}) {
-    {
-        check_det_scratch(det, R, "gs_rasterizer_backward_deterministic");
-        if (P <= 0) return 0;
-        const int tile = amr_mode != 0 ? 32 : 16;
-        const int T = ((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-        GeomView g;
-        ImageView img;
-        BinningView b;
-        carve_geom(geom_buffer, P, &g);
-        carve_image(img_buffer, (size_t)width * height, T, &img, tile);
-        carve_binning(binning_buffer, R, &b);
-        if (!radii) radii = g.radii;
-        const float* colors = colors_precomp ? colors_precomp : g.rgb;
-        if (amr_mode != 0) {
-            zero_accum_unless_clean(g, P, s);
-            if (R > 0) {
-                StageTimer _t(kRenderBwd, s);
-                launch_amr_render_backward(width, height, amr_mode, img, b, g, colors, background, dL_dpix, s);
-            }
-        } else {
-            blend_backward(det, width, height, P, R, img, b, g, radii, colors, background, dL_dpix, debug, s);
+int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
+    check_det_scratch(c.det, c.R, "gs_rasterizer_backward_deterministic");
+    BackwardGaussArgs a = c.a;
+    if (a.P <= 0) return 0;
+    hipStream_t s = c.s;
+    const Binned v = carve_buffers(c.geom_buffer, c.binning_buffer, c.img_buffer, a.P, c.R, c.width, c.height,
+                                   amr_mode != 0 ? 32 : 16);
+    const GeomView& g = v.g;
+    if (!a.radii) a.radii = v.radii;
+    const float* colors = c.colors_precomp ? c.colors_precomp : g.rgb;
+    if (amr_mode != 0) {
+        zero_accum_unless_clean(g, a.P, s);
+        if (c.R > 0) {
+            StageTimer _t(kRenderBwd, s);
+            launch_amr_render_backward(c.width, c.height, amr_mode, v.img, v.b, g, colors, c.background, c.dL_dpix, s);
         }
-        stage_check(debug != 0, s, "render_backward");
-        BackwardGaussArgs a;
-        a.P = P;
-        a.D = D;
-        a.M = M;
-        a.means3D = means3D;
-        a.radii = radii;
-        a.shs = shs;
-        a.scales = scales;
-        a.rotations = rotations;
-        a.scale_modifier = scale_modifier;
-        a.cov3D = cov3D_precomp ? cov3D_precomp : g.cov3D;
-        a.viewmatrix = viewmatrix;
-        a.projmatrix = projmatrix;
-        a.campos = campos;
-        a.focal_y = (float)height / (2.0f * tan_fovy);
-        a.focal_x = (float)width / (2.0f * tan_fovx);
-        a.tan_fovx = tan_fovx;
-        a.tan_fovy = tan_fovy;
-        a.has_cov_precomp = cov3D_precomp != nullptr;
-        a.drgb = g.drgb;  // read only where the header says this forward wrote the rows
-        a.drgb_known = a.drgb != nullptr && drgb_written(g.drgb);
-        a.hdr = g.hdr;
-        a.dL_dmean2D = dL_dmean2D;
-        a.dL_dconic = dL_dconic;
-        a.dL_dopacity = dL_dopacity;
-        a.dL_dcolor = dL_dcolor;
-        a.dL_dmean3D = dL_dmean3D;
-        a.dL_dcov3D = dL_dcov3D;
-        a.dL_dsh = dL_dsh;
-        a.dL_dscale = dL_dscale;
-        a.dL_drot = dL_drot;
-        { StageTimer _t(kBwdGauss, s); launch_backward_gaussians(a, g, s); }
-        stage_check(debug != 0, s, "preprocess_backward");
-        return 0;
+    } else {
+        blend_backward(c.det, c.width, c.height, a.P, c.R, v.img, v.b, g, a.radii, colors, c.background, c.dL_dpix,
+                       c.debug, s);
     }
+    stage_check(c.debug != 0, s, "render_backward");
+    a.cov3D = c.cov3D_precomp ? c.cov3D_precomp : g.cov3D;
+    a.has_cov_precomp = c.cov3D_precomp != nullptr;
+    a.focal_y = (float)c.height / (2.0f * a.tan_fovy);
+    a.focal_x = (float)c.width / (2.0f * a.tan_fovx);
+    a.drgb = g.drgb;  // read only where the header says this forward wrote the rows
+    a.drgb_known = a.drgb != nullptr && drgb_written(g.drgb);
+    a.hdr = g.hdr;
+    { StageTimer _t(kBwdGauss, s); launch_backward_gaussians(a, g, s); }
+    stage_check(c.debug != 0, s, "preprocess_backward");
+    return 0;
+}
+
+// Data-parallel stage 1: the blend backward of one view, packed into its view
+// record (c.out_record).
+int backward_view_grads_impl(const BackwardCall& c, const char* who) {
+    const BackwardGaussArgs& a = c.a;
+    if (a.P < 0) throw GsError(std::string(who) + ": negative P");
+    check_det_scratch(c.det, c.R, who);
+    hipStream_t s = c.s;
+    const Binned v = carve_buffers(c.geom_buffer, c.binning_buffer, c.img_buffer, a.P, c.R, c.width, c.height, 16);
+    const int* radii = a.radii ? a.radii : v.radii;
+    const float* colors = c.colors_precomp ? c.colors_precomp : v.g.rgb;
+    blend_backward(c.det, c.width, c.height, a.P, c.R, v.img, v.b, v.g, radii, colors, c.background, c.dL_dpix,
+                   c.debug, s);
+    stage_check(c.debug != 0, s, "render_backward");
+    launch_pack_view_grads(a.P, v.g, radii, c.colors_precomp == nullptr, a.viewmatrix, a.projmatrix, a.campos,
+                           c.width, c.height, a.tan_fovx, a.tan_fovy, c.out_record, s);
+    stage_check(c.debug != 0, s, "pack_view_grads");
+    return 0;
+}
+
+// What the two view-grads entries take, in their order (det: the caller's).
+BackwardCall view_grads_call(int P, int R, const float* background, int width, int height,
+                             const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
+                             const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                             char* geom_buffer, char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                             int debug, void* stream) {
+    BackwardCall c;
+    c.a.P = P;
+    c.R = R;
+    c.background = background;
+    c.width = width;
+    c.height = height;
+    c.colors_precomp = colors_precomp;
+    c.a.viewmatrix = viewmatrix;
+    c.a.projmatrix = projmatrix;
+    c.a.campos = campos;
+    c.a.tan_fovx = tan_fovx;
+    c.a.tan_fovy = tan_fovy;
+    c.a.radii = radii;
+    c.geom_buffer = geom_buffer;
+    c.binning_buffer = binning_buffer;
+    c.img_buffer = img_buffer;
+    c.dL_dpix = dL_dpix;
+    c.debug = debug;
+    c.s = static_cast<hipStream_t>(stream);
+    return c;
+}
+
+// What gs_rasterizer_backward, its deterministic form and the AMR backward
+// share, in their order: the above plus the per-Gaussian inputs and outputs.
+BackwardCall backward_call(int P, int D, int M, int R, const float* background, int width, int height,
+                           const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                           float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                           const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                           float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer,
+                           char* img_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic,
+                           float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                           float* dL_dscale, float* dL_drot, int debug, void* stream) {
+    BackwardCall c = view_grads_call(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix, campos,
+                                     tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                     debug, stream);
+    c.a.D = D;
+    c.a.M = M;
+    c.a.means3D = means3D;
+    c.a.shs = shs;
+    c.a.scales = scales;
+    c.a.scale_modifier = scale_modifier;
+    c.a.rotations = rotations;
+    c.cov3D_precomp = cov3D_precomp;
+    c.a.dL_dmean2D = dL_dmean2D;
+    c.a.dL_dconic = dL_dconic;
+    c.a.dL_dopacity = dL_dopacity;
+    c.a.dL_dcolor = dL_dcolor;
+    c.a.dL_dmean3D = dL_dmean3D;
+    c.a.dL_dcov3D = dL_dcov3D;
+    c.a.dL_dsh = dL_dsh;
+    c.a.dL_dscale = dL_dscale;
+    c.a.dL_drot = dL_drot;
+    return c;
 }
 }  // namespace
 
@@ -736,11 +859,12 @@ int gs_rasterizer_backward(int P, int D, int M, int R, const float* background, 
                            float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
                            float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream) {
     return guarded([&]() -> int {
-        return rasterizer_backward_impl(0, P, D, M, R, background, width, height, means3D, shs, colors_precomp,
-                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
-                                        dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                        dL_dsh, dL_dscale, dL_drot, debug, static_cast<hipStream_t>(stream));
+        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                       dL_dscale, dL_drot, debug, stream);
+        return rasterizer_backward_impl(0, c);
     });
 }
 
@@ -759,22 +883,19 @@ int gs_amr_rasterizer_backward(int P, int D, int M, int R, const float* backgrou
         if (foveaStep > 4) throw GsError("gs_amr_rasterizer_backward: foveaStep 1..4 or < 0 (render_once)");
         if (interpolate_image && foveaStep > 0)
             throw GsError("gs_amr_rasterizer_backward: interpolate_image is supported for render_once only");
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const float* g = dL_dpix;
+        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                       dL_dscale, dL_drot, debug, stream);
         if (interpolate_image && P > 0) {
             if (!dL_dpix_scratch) throw GsError("gs_amr_rasterizer_backward: interpolation needs dL_dpix_scratch");
-            const int T = ((width + 31) / 32) * ((height + 31) / 32);
-            ImageView img;
-            carve_image(img_buffer, (size_t)width * height, T, &img, 32);
-            launch_amr_interp_fold(width, height, img, dL_dpix, dL_dpix_scratch, s);
-            stage_check(debug != 0, s, "amr_interp_fold");
-            g = dL_dpix_scratch;
+            launch_amr_interp_fold(width, height, image_view(img_buffer, width, height, 32), dL_dpix, dL_dpix_scratch,
+                                   c.s);
+            stage_check(debug != 0, c.s, "amr_interp_fold");
+            c.dL_dpix = dL_dpix_scratch;
         }
-        return rasterizer_backward_impl(foveaStep, P, D, M, R, background, width, height, means3D, shs,
-                                        colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix,
-                                        projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
-                                        img_buffer, g, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D,
-                                        dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, s);
+        return rasterizer_backward_impl(foveaStep, c);
     });
 }
 
@@ -794,47 +915,15 @@ int gs_rasterizer_backward_deterministic(int P, int D, int M, int R, const float
                                          float* dL_dsh, float* dL_dscale, float* dL_drot, char* scratch,
                                          size_t scratch_bytes, int debug, void* stream) {
     return guarded([&]() -> int {
-        DetScratch det;
-        det.on = true;
-        det.base = scratch;
-        det.bytes = scratch_bytes;
-        return rasterizer_backward_impl(0, P, D, M, R, background, width, height, means3D, shs, colors_precomp,
-                                        scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
-                                        dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D,
-                                        dL_dsh, dL_dscale, dL_drot, debug, static_cast<hipStream_t>(stream), det);
+        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                       dL_dscale, dL_drot, debug, stream);
+        c.det = DetScratch{true, scratch, scratch_bytes};
+        return rasterizer_backward_impl(0, c);
     });
 }
-
-namespace {
-int backward_view_grads_impl(int P, int R, const float* background, int width, int height,
-                             const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
-                             const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                             char* geom_buffer, char* binning_buffer, char* img_buffer, const float* dL_dpix,
-                             float* out_record, int debug, void* stream, const DetScratch& det, const char* who) {
-    {
-        if (P < 0) throw GsError(std::string(who) + ": negative P");
-        check_det_scratch(det, R, who);
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const int tile = 16;
-        const int T = ((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-        GeomView g;
-        ImageView img;
-        BinningView b;
-        carve_geom(geom_buffer, P, &g);
-        carve_image(img_buffer, (size_t)width * height, T, &img, tile);
-        carve_binning(binning_buffer, R, &b);
-        if (!radii) radii = g.radii;
-        const float* colors = colors_precomp ? colors_precomp : g.rgb;
-        blend_backward(det, width, height, P, R, img, b, g, radii, colors, background, dL_dpix, debug, s);
-        stage_check(debug != 0, s, "render_backward");
-        launch_pack_view_grads(P, g, radii, colors_precomp == nullptr, viewmatrix, projmatrix, campos, width, height,
-                               tan_fovx, tan_fovy, out_record, s);
-        stage_check(debug != 0, s, "pack_view_grads");
-        return 0;
-    }
-}
-}  // namespace
 
 int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int width, int height,
                                       const float* colors_precomp, const float* viewmatrix, const float* projmatrix,
@@ -842,10 +931,11 @@ int gs_rasterizer_backward_view_grads(int P, int R, const float* background, int
                                       char* geom_buffer, char* binning_buffer, char* img_buffer,
                                       const float* dL_dpix, float* out_record, int debug, void* stream) {
     return guarded([&]() -> int {
-        return backward_view_grads_impl(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
-                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
-                                        dL_dpix, out_record, debug, stream, DetScratch{},
-                                        "gs_rasterizer_backward_view_grads");
+        BackwardCall c = view_grads_call(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
+                                         campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
+                                         dL_dpix, debug, stream);
+        c.out_record = out_record;
+        return backward_view_grads_impl(c, "gs_rasterizer_backward_view_grads");
     });
 }
 
@@ -857,14 +947,12 @@ int gs_rasterizer_backward_view_grads_deterministic(int P, int R, const float* b
                                                     float* out_record, char* scratch, size_t scratch_bytes,
                                                     int debug, void* stream) {
     return guarded([&]() -> int {
-        DetScratch det;
-        det.on = true;
-        det.base = scratch;
-        det.bytes = scratch_bytes;
-        return backward_view_grads_impl(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
-                                        campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
-                                        dL_dpix, out_record, debug, stream, det,
-                                        "gs_rasterizer_backward_view_grads_deterministic");
+        BackwardCall c = view_grads_call(P, R, background, width, height, colors_precomp, viewmatrix, projmatrix,
+                                         campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer,
+                                         dL_dpix, debug, stream);
+        c.out_record = out_record;
+        c.det = DetScratch{true, scratch, scratch_bytes};
+        return backward_view_grads_impl(c, "gs_rasterizer_backward_view_grads_deterministic");
     });
 }
 
@@ -1129,35 +1217,26 @@ int gs_amr_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffe
                                  int foveaStep, const float* out_color_precomp, char* geom_buffer_precomp,
                                  char* binning_buffer_precomp, char* image_buffer_precomp, float* out_color,
                                  int* radii, int interpolate_image, int debug, int num_rendered_hint, void* stream) {
-    t_store_drgb = !take_fwd_no_grad();
-    const bool step0_unfilled = t_amr_step0_unfilled != 0;  // (one-shot, consumed by every AMR forward)
-    t_amr_step0_unfilled = 0;
+    const ForwardIn in = forward_in(true, P, D, M, background, width, height, means3D, shs, colors_precomp, opacities,
+                                    scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                    tan_fovx, tan_fovy, prefiltered);
     return guarded([&]() -> int {
         if (P <= 0) return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
         const int tile = 32;
         const int W = width, H = height;
-        const int T = ((W + tile - 1) / tile) * ((H + tile - 1) / tile);
         const bool dbg = debug != 0;
         if (foveaStep >= 1) {
             // amr/cr/rasterizer_impl.cu:334-462: progressive step on precomputed buffers.
             if (!geom_buffer_precomp || !image_buffer_precomp)
                 throw GsError("foveaStep >= 1 needs the buffers returned by foveaStep 0");
-            GeomView g;
-            ImageView img;
-            BinningView b;
-            carve_geom(geom_buffer_precomp, P, &g);
-            carve_image(image_buffer_precomp, (size_t)W * H, T, &img, 32);
-            int K = num_rendered_hint;
-            if (K < 0) {  // the reference reads K back here (amr/cr/rasterizer_impl.cu:337-340)
-                uint32_t hdr[4];
-                read_header(g.hdr, hdr, s);
-                K = (int)hdr[kHdrNumRendered];
-            }
-            if (K > 0 && !binning_buffer_precomp)
-                throw GsError("foveaStep >= 1 needs the binning buffer returned by foveaStep 0");
-            AmrBinningView ab;
-            carve_binning(binning_buffer_precomp, K, &b, &ab);
+            const int K = rendered_count(num_rendered_hint, geom_buffer_precomp, P, binning_buffer_precomp, s,
+                                         "foveaStep >= 1 needs the binning buffer returned by foveaStep 0");
+            const Binned v = carve_buffers(geom_buffer_precomp, binning_buffer_precomp, image_buffer_precomp, P, K, W,
+                                           H, tile, true);
+            const GeomView& g = v.g;
+            const ImageView& img = v.img;
+            const int T = v.T;
             // variant 4 folds the step's level update and zero radii into its
             // render launch, and writes the zeros of the pixels it does not render
             const bool fused = g_amr_variant == 4;
@@ -1168,7 +1247,7 @@ int gs_amr_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffe
             }
             const float* feats = colors_precomp ? colors_precomp : g.rgb;
             { StageTimer _t(kAmrRender, s);
-              launch_amr_render(W, H, img, fused ? img.levels : img.levels_current, img.levels_last, b, ab, g, feats,
+              launch_amr_render(W, H, img, fused ? img.levels : img.levels_current, img.levels_last, v.b, v.ab, g, feats,
                                 background, out_color, foveaStep, s, fused, P, radii); }
             stage_check(dbg, s, "amr_render");
             if (interpolate_image) {
@@ -1179,8 +1258,6 @@ int gs_amr_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffe
             }
             return K;
         }
-        ForwardIn in{P, D, M, background, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                     viewmatrix, projmatrix, cam_pos, width, height, scale_modifier, tan_fovx, tan_fovy, prefiltered};
         // Everything that needs the tile counts / ranges but not K runs behind
         // the K copy, while the host waits for it: the levels (percentiles of
         // the counts), the step's level schedule, the tile order (by list
@@ -1188,7 +1265,7 @@ int gs_amr_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffe
         auto before_k = [&](Binned& r) {
             // (variant 4 writes the zeros of the pixels it does not render;
             // otherwise, and at foveaStep 0, the levels launch zeroes the image)
-            const bool zero_img = (foveaStep == 0 && !step0_unfilled) || g_amr_variant != 4;
+            const bool zero_img = (foveaStep == 0 && !in.step0_unfilled) || g_amr_variant != 4;
             { StageTimer _t(kAmrLevels, s);
               launch_amr_levels(r.T, r.img, s, zero_img ? out_color : nullptr, zero_img ? 3 * (size_t)W * H : 0); }
             stage_check(dbg, s, "amr_levels");
@@ -1244,26 +1321,14 @@ int gs_amr_accumulate_step(int P, const float* background, int width, int height
             throw GsError("gs_amr_accumulate_step needs the buffers returned by foveaStep 0 and the running image");
         hipStream_t s = static_cast<hipStream_t>(stream);
         const int W = width, H = height;
-        const int T = ((W + 31) / 32) * ((H + 31) / 32);
-        GeomView g;
-        ImageView img;
-        BinningView b;
-        carve_geom(geom_buffer_precomp, P, &g);
-        carve_image(image_buffer_precomp, (size_t)W * H, T, &img, 32);
-        int K = num_rendered_hint;
-        if (K < 0) {
-            uint32_t hdr[4];
-            read_header(g.hdr, hdr, s);
-            K = (int)hdr[kHdrNumRendered];
-        }
-        if (K > 0 && !binning_buffer_precomp)
-            throw GsError("gs_amr_accumulate_step needs the binning buffer returned by foveaStep 0");
-        AmrBinningView ab;
-        carve_binning(binning_buffer_precomp, K, &b, &ab);
-        const float* feats = colors_precomp ? colors_precomp : g.rgb;
+        const int K = rendered_count(num_rendered_hint, geom_buffer_precomp, P, binning_buffer_precomp, s,
+                                     "gs_amr_accumulate_step needs the binning buffer returned by foveaStep 0");
+        const Binned v = carve_buffers(geom_buffer_precomp, binning_buffer_precomp, image_buffer_precomp, P, K, W, H,
+                                       32, true);
+        const float* feats = colors_precomp ? colors_precomp : v.g.rgb;
         { StageTimer _t(kAmrRender, s);
-          launch_amr_render(W, H, img, img.levels, img.levels_last, b, ab, g, feats, background, accum, foveaStep, s,
-                            true, split ? 4 * P : P, radii, split ? 2 : fill ? 0 : 1); }
+          launch_amr_render(W, H, v.img, v.img.levels, v.img.levels_last, v.b, v.ab, v.g, feats, background, accum,
+                            foveaStep, s, true, split ? 4 * P : P, radii, split ? 2 : fill ? 0 : 1); }
         stage_check(debug != 0, s, "amr_render (accumulate)");
         return K;
     });
@@ -1275,13 +1340,11 @@ int gs_amr_set_step_state(char* image_buffer, size_t image_buffer_bytes, int wid
         if (step < 1 || step > 4) throw GsError("gs_amr_set_step_state: step in 1..4");
         if (width <= 0 || height <= 0) return 0;
         if (!image_buffer) throw GsError("gs_amr_set_step_state: needs the image buffer of foveaStep 0");
-        const size_t T = (size_t)((width + 31) / 32) * ((height + 31) / 32);
-        if (image_buffer_bytes < carve_image(nullptr, (size_t)width * height, T, nullptr, 32))
+        if (image_buffer_bytes < gs_image_bytes(width, height, 32))
             throw GsError("gs_amr_set_step_state: image buffer too small for width x height");
-        ImageView img;
-        carve_image(image_buffer, (size_t)width * height, T, &img, 32);
         hipStream_t s = static_cast<hipStream_t>(stream);
-        launch_fovea_levels(kAmrStateAfter + step, (int)T, img, s);
+        launch_fovea_levels(kAmrStateAfter + step, tile_count(width, height, 32),
+                            image_view(image_buffer, width, height, 32), s);
         stage_check(false, s, "amr_set_step_state");
         return 0;
     });
@@ -1301,14 +1364,11 @@ int gs_amr_fovea_levels(char* image_buffer, size_t image_buffer_bytes, int width
             r[k] = radii[k];
             if (!(r[k] >= 0.f)) throw GsError("gs_amr_fovea_levels: radii must be >= 0");
         }
-        const int tile = 32;
-        const size_t T = (size_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-        if (image_buffer_bytes < carve_image(nullptr, (size_t)width * height, T, nullptr, tile))
+        if (image_buffer_bytes < gs_image_bytes(width, height, 32))
             throw GsError("gs_amr_fovea_levels: image buffer too small for width x height");
-        ImageView img;
-        carve_image(image_buffer, (size_t)width * height, T, &img, tile);
         hipStream_t s = static_cast<hipStream_t>(stream);
-        launch_fovea_override(width, height, img, nfovea, cx, cy, r, min_level, replace, s);
+        launch_fovea_override(width, height, image_view(image_buffer, width, height, 32), nfovea, cx, cy, r, min_level,
+                              replace, s);
         stage_check(false, s, "amr_fovea_levels");
         return 0;
     });
@@ -1393,84 +1453,67 @@ int gs_activation_backward(int P, int M, int accumulate, const float* dL_dshs, c
 // Process-wide performance choices, each the default or one fallback; every
 // pair produces the same results (bit-identical buffers, sums equal to
 // atomic-order noise), so they are safe to flip between calls.
+namespace {
+struct TuningKey {
+    const char* key;
+    const int* value;  // as gs_get_tuning reports it: 0 = the fallback, else the default's number
+    void (*set)(int);
+};
+const TuningKey kTuning[] = {
+    // 0: one wave x 4 px predicate form; else the default
+    {"fwd_variant", &g_fwd_variant, set_forward_variant},
+    // 0: predicate form, LDS-row sums; else the default (opacity-scaled sums)
+    {"bwd_variant", &g_bwd_variant, set_backward_variant},
+    // 0: full-list AMR blocks; else region sub-lists (default)
+    {"amr_variant", &g_amr_variant, set_amr_variant},
+    // 0: bitonic networks only; 1: per-tile bucket sort (default)
+    {"sort_algo", &g_sort_algo, set_sort_algo},
+    // 0: no row-group cull in the blends (the exactness A/B)
+    {"cull", &g_cull, set_cull},
+    // 2: polled K read-back (default); 0: copy + event
+    {"hdr_mirror", &g_hdr_mirror, [](int v) { g_hdr_mirror = v == 0 ? 0 : 2; }},
+    // speculative duplicate before the K read-back (base forward)
+    {"spec_dup", &g_spec_dup, [](int v) { g_spec_dup = v; }},
+    // 0: the SGPR-weight FMA convolution; 1: matrix cores (default)
+    {"ritnet_mfma", &g_ritnet_mfma, set_ritnet_mfma},
+};
+
+const TuningKey* tuning_key(const char* key) {
+    for (const TuningKey& e : kTuning)
+        if (key && std::strcmp(key, e.key) == 0) return &e;
+    if (key) g_err = std::string("unknown tuning key ") + key;
+    return nullptr;
+}
+}  // namespace
+
 int gs_set_tuning(const char* key, int value) {
-    if (!key) return -1;
-    if (std::strcmp(key, "fwd_variant") == 0) {  // 0: one wave x 4 px predicate form; else the default
-        set_forward_variant(value);
-        return 0;
-    }
-    if (std::strcmp(key, "bwd_variant") == 0) {  // 0: predicate form, LDS-row sums; else the default (opacity-scaled sums)
-        set_backward_variant(value);
-        return 0;
-    }
-    if (std::strcmp(key, "amr_variant") == 0) {  // 0: full-list AMR blocks; else region sub-lists (default)
-        set_amr_variant(value);
-        return 0;
-    }
-    if (std::strcmp(key, "sort_algo") == 0) {  // 0: bitonic networks only; 1: per-tile bucket sort (default)
-        set_sort_algo(value);
-        return 0;
-    }
-    if (std::strcmp(key, "cull") == 0) {  // 0: no row-group cull in the blends (the exactness A/B)
-        set_cull(value);
-        return 0;
-    }
-    if (std::strcmp(key, "hdr_mirror") == 0) {  // 2: polled K read-back (default); 0: copy + event
-        g_hdr_mirror = value == 0 ? 0 : 2;
-        return 0;
-    }
-    if (std::strcmp(key, "spec_dup") == 0) {  // speculative duplicate before the K read-back (base forward)
-        g_spec_dup = value;
-        return 0;
-    }
-    if (std::strcmp(key, "ritnet_mfma") == 0) {  // 0: the SGPR-weight FMA convolution; 1: matrix cores (default)
-        set_ritnet_mfma(value);
-        return 0;
-    }
-    g_err = std::string("unknown tuning key ") + key;
-    return -1;
+    const TuningKey* e = tuning_key(key);
+    if (e) e->set(value);
+    return e ? 0 : -1;
 }
 
-// The current value of a gs_set_tuning key (the variants as they are used:
-// 0 = the fallback, else the default's number).
+// The current value of a gs_set_tuning key.
 int gs_get_tuning(const char* key, int* value) {
     if (!key || !value) return -1;
     hdr_mirror_on();  // (resolves the GSAMD_HDR_MIRROR default)
-    const struct { const char* k; const int* v; } table[] = {
-        {"fwd_variant", &g_fwd_variant}, {"bwd_variant", &g_bwd_variant}, {"amr_variant", &g_amr_variant},
-        {"sort_algo", &g_sort_algo},     {"cull", &g_cull},               {"hdr_mirror", &g_hdr_mirror},
-        {"spec_dup", &g_spec_dup},       {"ritnet_mfma", &g_ritnet_mfma}};
-    for (const auto& e : table)
-        if (std::strcmp(key, e.k) == 0) {
-            *value = *e.v;
-            return 0;
-        }
-    g_err = std::string("unknown tuning key ") + key;
-    return -1;
+    const TuningKey* e = tuning_key(key);
+    if (!e) return -1;
+    *value = *e->value;
+    return 0;
 }
 
 int gs_set_thread_option(const char* key, int value) {
     if (!key) return -1;
-    if (std::strcmp(key, "fwd_no_grad") == 0) {
-        t_fwd_no_grad = value;
-        return 0;
-    }
-    if (std::strcmp(key, "sh_drgb") == 0) {
-        t_sh_drgb = value;
-        return 0;
-    }
-    if (std::strcmp(key, "store_cov3d") == 0) {
-        t_store_cov3d = value;
-        return 0;
-    }
-    if (std::strcmp(key, "fwd_zero") == 0) {
-        t_fwd_zero = value;
-        return 0;
-    }
-    if (std::strcmp(key, "amr_step0_unfilled") == 0) {
-        t_amr_step0_unfilled = value;
-        return 0;
-    }
+    const struct { const char* key; int* value; } table[] = {{"fwd_no_grad", &t_fwd_no_grad},
+                                                             {"sh_drgb", &t_sh_drgb},
+                                                             {"store_cov3d", &t_store_cov3d},
+                                                             {"fwd_zero", &t_fwd_zero},
+                                                             {"amr_step0_unfilled", &t_amr_step0_unfilled}};
+    for (const auto& e : table)
+        if (std::strcmp(key, e.key) == 0) {
+            *e.value = value;
+            return 0;
+        }
     g_err = std::string("unknown thread option ") + key;
     return -1;
 }
@@ -1507,8 +1550,7 @@ size_t gs_geom_bytes(int P) { return carve_geom(nullptr, (size_t)P, nullptr); }
 size_t gs_amr_geom_bytes(int P) { return carve_geom(nullptr, (size_t)P, nullptr, true, true); }
 
 size_t gs_image_bytes(int width, int height, int tile) {
-    const size_t T = (size_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-    return carve_image(nullptr, (size_t)width * height, T, nullptr, tile);
+    return carve_image(nullptr, (size_t)width * height, tile_count(width, height, tile), nullptr, tile);
 }
 
 size_t gs_binning_bytes(int K) { return carve_binning(nullptr, (size_t)K, nullptr); }
@@ -1542,9 +1584,7 @@ int gs_geom_view_of(char* base, int P, gs_geom_view* out) {
 }
 
 int gs_image_view_of(char* base, int width, int height, int tile, gs_image_view* out) {
-    const size_t T = (size_t)((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-    ImageView v;
-    carve_image(base, (size_t)width * height, T, &v, tile);
+    const ImageView v = image_view(base, width, height, tile);
     static_assert(sizeof(ImageView) == sizeof(gs_image_view), "view layout");
     std::memcpy(out, &v, sizeof(v));
     return 0;
@@ -1561,14 +1601,8 @@ int gs_binning_view_of(char* base, int K, gs_binning_view* out) {
 int gs_reconstruct_keys(char* geom_buffer, char* binning_buffer, char* img_buffer, int P, int K, int width,
                         int height, int tile, uint64_t* keys_out, void* stream) {
     return guarded([&]() -> int {
-        const int T = ((width + tile - 1) / tile) * ((height + tile - 1) / tile);
-        GeomView g;
-        ImageView img;
-        BinningView b;
-        carve_geom(geom_buffer, P, &g);
-        carve_image(img_buffer, (size_t)width * height, T, &img, tile);
-        carve_binning(binning_buffer, K, &b);
-        if (K > 0) launch_reconstruct_keys(T, img, b, g, keys_out, static_cast<hipStream_t>(stream));
+        const Binned v = carve_buffers(geom_buffer, binning_buffer, img_buffer, P, K, width, height, tile);
+        if (K > 0) launch_reconstruct_keys(v.T, v.img, v.b, v.g, keys_out, static_cast<hipStream_t>(stream));
         stage_check(false, static_cast<hipStream_t>(stream), "reconstruct_keys");
         return 0;
     });

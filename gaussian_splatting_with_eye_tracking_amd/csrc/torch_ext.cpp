@@ -18,6 +18,7 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <optional>
 #include <string>
 #include <tuple>
 #include <vector>
@@ -105,36 +106,154 @@ float* fptr_mut(Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
 // step runs as usual.  Final T and n_contrib are those of every round from
 // step 1 on (each pixel belongs to one round; the rounds' values are the
 // same either way).  _C.set_amr_speculation(False) turns it off.
+//
+// What a tensor the cached images depend on was when they were rendered: its
+// storage, address and version.  The address alone is no identity: once the
+// tensor is freed the caching allocator can hand the same address to a new
+// tensor, which also starts at version 0.  The storage is held weakly, so the
+// cache keeps no buffer alive; views of one storage at one address match.
+struct TensorId {
+    std::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> storage;  // none: an empty tensor
+    const void* ptr = nullptr;
+    int64_t version = -1;
+    explicit TensorId(const Tensor& t) {
+        if (!t.defined() || t.numel() == 0) return;
+        storage = t.storage().getWeakStorageImpl();
+        ptr = t.data_ptr();
+        version = (int64_t)t._version();
+    }
+    bool same_memory(const TensorId& o) const {
+        if (ptr != o.ptr || storage.has_value() != o.storage.has_value()) return false;
+        return !storage || (!storage->expired() && storage->_unsafe_get_target() == o.storage->_unsafe_get_target());
+    }
+    bool operator==(const TensorId& o) const { return version == o.version && same_memory(o); }
+};
+
+struct SpecKey {
+    TensorId g, b, im, bg, col;  // step 0's buffers; the caller's background and colors_precomp
+    int W, H, P;
+    void* stream;
+    bool same_buffers(const SpecKey& o) const {
+        return g.same_memory(o.g) && b.same_memory(o.b) && im.same_memory(o.im);
+    }
+    bool operator==(const SpecKey& o) const {
+        return g == o.g && b == o.b && im == o.im && bg == o.bg && col == o.col && W == o.W && H == o.H && P == o.P &&
+               stream == o.stream;
+    }
+};
+
 struct SpecSteps {
-    const void* g = nullptr;
-    const void* b = nullptr;
-    const void* im = nullptr;
-    int64_t vg = 0, vb = 0, vim = 0, vbg = 0, vcol = 0;
-    const void* bg = nullptr;
-    const void* col = nullptr;
-    int W = 0, H = 0, P = 0, K = 0, next = 0;  // next: the step served next (2..4); 0 = nothing cached
-    size_t im_bytes = 0;
-    void* stream = nullptr;
+    std::optional<SpecKey> key;
+    int K = 0, next = 0;   // next: the step served next (2..4); 0 = nothing cached
     Tensor images, radii;  // [4, 3, H, W], [4, P]
     void clear() {
         next = 0;
+        key.reset();
         images = Tensor();
         radii = Tensor();
-        g = b = im = bg = col = nullptr;
     }
 };
 thread_local SpecSteps t_spec;
 thread_local bool t_spec_on = true;
 
-int64_t version_of(const Tensor& t) { return t.defined() && t.numel() ? (int64_t)t._version() : -1; }
+using Forward6 = std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
-std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_impl(
-    bool amr, const Tensor& background, const Tensor& means3D_in, const Tensor& colors_in, const Tensor& opacity_in,
-    const Tensor& scales_in, const Tensor& rotations_in, float scale_modifier, const Tensor& cov3D_precomp_in,
-    const Tensor& viewmatrix_in, const Tensor& projmatrix_in, float tan_fovx, float tan_fovy, int image_height,
-    int image_width, const Tensor& sh_in, int degree, const Tensor& campos_in, bool prefiltered, int foveaStep,
-    const Tensor& out_color_precomp_in, const Tensor& geom_pre, const Tensor& bin_pre, const Tensor& img_pre,
-    bool interpolate_image, bool debug) {
+char* bptr(const Tensor& t) { return t.numel() ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; }
+
+// One forward's operands, contiguous and checked, its scalar arguments and
+// its outputs: the image, the radii and the three buffers the library sizes.
+struct ForwardCall {
+    Tensor bg, means3D, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos;
+    Tensor out_color, radii, geom, binning, image;
+    int P, M, W, H, degree;
+    float scale_modifier, tan_fovx, tan_fovy;
+    bool prefiltered, debug;
+    void* stream;
+};
+
+Forward6 base_forward(ForwardCall& o) {
+    const int rendered = gs_rasterizer_forward(
+        buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
+        fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
+        fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
+        o.prefiltered, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(), o.debug, o.stream);
+    check(rendered, "rasterize_gaussians");
+    return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
+}
+
+// Step `step` from the cache, or nothing: a miss.  A miss on the speculated
+// buffers sets their level state back to that after the last step served.
+std::optional<Forward6> spec_serve(const SpecKey& key, int step, bool plain, const Tensor& g, const Tensor& b,
+                                   const Tensor& im) {
+    SpecSteps& sp = t_spec;
+    if (step <= 1) sp.clear();  // a new frame (or a new step 1): nothing cached survives it
+    if (sp.next == 0 || step > 4 || !sp.key->same_buffers(key)) return std::nullopt;
+    if (sp.next == step && plain && *sp.key == key) {
+        Forward6 r = std::make_tuple(sp.K, sp.images[step - 1], sp.radii[step - 1], g, b, im);
+        if (step == 4) sp.clear();
+        else sp.next = step + 1;
+        return r;
+    }
+    check(gs_amr_set_step_state(bptr(im), (size_t)im.numel(), key.W, key.H, sp.next - 1, key.stream),
+          "amr speculation (level state)");
+    sp.clear();
+    return std::nullopt;
+}
+
+// Step 1: the images and radii of steps 1..4 in one launch, cached under `key`.
+Forward6 spec_fill(SpecKey key, const ForwardCall& o, int hint, const Tensor& g, const Tensor& b,
+                   const Tensor& im) {
+    Tensor imgs = torch::empty({4, 3, o.H, o.W}, o.means3D.options());
+    Tensor rads = torch::empty({4, o.P}, o.means3D.options().dtype(torch::kInt32));
+    const int rendered =
+        gs_amr_accumulate_step(o.P, fptr(o.bg), o.W, o.H, fptr(o.colors), GSPLAT_AMD_AMR_STEPS_1_TO_4_SPLIT, bptr(g),
+                               bptr(b), bptr(im), imgs.data_ptr<float>(), rads.data_ptr<int>(), 0, hint, o.stream);
+    check(rendered, "rasterize_gaussians (AMR, speculative steps 1..4)");
+    SpecSteps& sp = t_spec;
+    sp.key = std::move(key);
+    sp.K = rendered;
+    sp.images = imgs;
+    sp.radii = rads;
+    sp.next = 2;
+    return std::make_tuple(rendered, imgs[0], rads[0], g, b, im);
+}
+
+// `background` / `colors_in`: the caller's tensors behind o.bg / o.colors (the cache is keyed on them).
+Forward6 amr_forward(ForwardCall& o, const Tensor& background, const Tensor& colors_in, int foveaStep,
+                     const Tensor& out_color_precomp_in, const Tensor& g, const Tensor& b, const Tensor& im,
+                     bool interpolate_image) {
+    const Tensor pre = out_color_precomp_in.contiguous();
+    require_like(pre, o.means3D, "out_color_precomp", 3LL * o.H * o.W);
+    for (const Tensor* bt : {&g, &b, &im}) require_like(*bt, o.means3D, "precomp buffer", -1, torch::kByte);
+    // K of the precomputed buffers from the binning buffer's size (no sync)
+    const int hint = foveaStep >= 1 ? gs_amr_binning_count_of_bytes((size_t)b.numel()) : -1;
+    const bool plain = !interpolate_image && !o.debug;
+    SpecKey key{TensorId(g), TensorId(b), TensorId(im), TensorId(background), TensorId(colors_in),
+                o.W,         o.H,         o.P,          o.stream};
+    if (auto served = spec_serve(key, foveaStep, plain, g, b, im)) return *served;
+    int amr_variant = 0;
+    check(gs_get_tuning("amr_variant", &amr_variant), "get_tuning");
+    if (foveaStep == 1 && t_spec_on && plain && amr_variant == 4 && g.numel() && im.numel())
+        return spec_fill(std::move(key), o, hint, g, b, im);
+    const int rendered = gs_amr_rasterizer_forward_ex(
+        buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
+        fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
+        fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
+        o.prefiltered, foveaStep, fptr(pre), bptr(g), bptr(b), bptr(im), o.out_color.data_ptr<float>(),
+        o.radii.data_ptr<int>(), interpolate_image, o.debug, hint, o.stream);
+    check(rendered, "rasterize_gaussians (AMR)");
+    if (foveaStep > 0)  // amr/rasterize_points.cu:182-190: hand the precomputed buffers back
+        return std::make_tuple(rendered, o.out_color, o.radii, g, b, im);
+    return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
+}
+
+Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3D_in, const Tensor& colors_in,
+                        const Tensor& opacity_in, const Tensor& scales_in, const Tensor& rotations_in,
+                        float scale_modifier, const Tensor& cov3D_precomp_in, const Tensor& viewmatrix_in,
+                        const Tensor& projmatrix_in, float tan_fovx, float tan_fovy, int image_height, int image_width,
+                        const Tensor& sh_in, int degree, const Tensor& campos_in, bool prefiltered, int foveaStep,
+                        const Tensor& out_color_precomp_in, const Tensor& geom_pre, const Tensor& bin_pre,
+                        const Tensor& img_pre, bool interpolate_image, bool debug) {
     if (means3D_in.ndimension() != 2 || means3D_in.size(1) != 3) {
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     }
@@ -144,109 +263,49 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> rasterize_impl(
     const at::OptionalDeviceGuard guard(device_of(means3D_in));
     require_device(means3D_in, "means3D");
     auto float_opts = means3D_in.options().dtype(torch::kFloat32);
-    // both forwards write every pixel (the AMR one zeros where it renders nothing)
-    Tensor out_color = P == 0 ? torch::zeros({3, H, W}, float_opts) : torch::empty({3, H, W}, float_opts);
-    // (the AMR steps >= 1 write their zero radii in the fovea-levels launch)
-    Tensor radii = P == 0 ? torch::zeros({P}, means3D_in.options().dtype(torch::kInt32))
-                          : torch::empty({P}, means3D_in.options().dtype(torch::kInt32));
+    auto int_opts = means3D_in.options().dtype(torch::kInt32);
     auto byte_opts = means3D_in.options().dtype(torch::kByte);
-    Tensor geomBuffer = torch::empty({0}, byte_opts);
-    Tensor binningBuffer = torch::empty({0}, byte_opts);
-    Tensor imgBuffer = torch::empty({0}, byte_opts);
-    int rendered = 0;
-    if (P != 0) {
-        const Tensor bg = background.contiguous(), means3D = means3D_in.contiguous(), colors = colors_in.contiguous(),
-                     opacity = opacity_in.contiguous(), scales = scales_in.contiguous(),
-                     rotations = rotations_in.contiguous(), cov3D_precomp = cov3D_precomp_in.contiguous(),
-                     viewmatrix = viewmatrix_in.contiguous(), projmatrix = projmatrix_in.contiguous(),
-                     sh = sh_in.contiguous(), campos = campos_in.contiguous();
-        check_operands(means3D, P, bg, colors, opacity, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh,
-                       campos);
-        const int M = sh.size(0) != 0 ? (int)sh.size(1) : 0;
-        void* stream = stream_of(means3D);
-        if (!amr) {
-            rendered = gs_rasterizer_forward(buf_of(geomBuffer), buf_of(binningBuffer), buf_of(imgBuffer), P, degree, M,
-                                             fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(opacity),
-                                             fptr(scales), scale_modifier, fptr(rotations), fptr(cov3D_precomp),
-                                             fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx, tan_fovy,
-                                             prefiltered, out_color.data_ptr<float>(), radii.data_ptr<int>(), debug,
-                                             stream);
-            check(rendered, "rasterize_gaussians");
-        } else {
-            const Tensor pre = out_color_precomp_in.contiguous();
-            require_like(pre, means3D, "out_color_precomp", 3LL * H * W);
-            for (const Tensor* bt : {&geom_pre, &bin_pre, &img_pre}) require_like(*bt, means3D, "precomp buffer", -1, torch::kByte);
-            Tensor g = geom_pre, b = bin_pre, im = img_pre;
-            // K of the precomputed buffers from the binning buffer's size (no sync)
-            const int hint = foveaStep >= 1 ? gs_amr_binning_count_of_bytes((size_t)b.numel()) : -1;
-            SpecSteps& sp = t_spec;
-            const bool same_bufs = sp.next != 0 && g.numel() && im.numel() && sp.g == g.data_ptr() &&
-                                   sp.im == im.data_ptr() && sp.b == (b.numel() ? b.data_ptr() : nullptr);
-            if (foveaStep >= 2 && foveaStep <= 4 && same_bufs) {
-                if (sp.next == foveaStep && !interpolate_image && !debug && sp.vg == version_of(g) &&
-                    sp.vb == version_of(b) && sp.vim == version_of(im) && sp.bg == bg.data_ptr() &&
-                    sp.vbg == version_of(background) && sp.col == (colors.numel() ? colors.data_ptr() : nullptr) &&
-                    sp.vcol == version_of(colors_in) && sp.W == W && sp.H == H && sp.P == P && sp.stream == stream) {
-                    Tensor img_k = sp.images[foveaStep - 1], rad_k = sp.radii[foveaStep - 1];
-                    const int K = sp.K;
-                    if (foveaStep == 4) sp.clear();
-                    else sp.next = foveaStep + 1;
-                    return std::make_tuple(K, img_k, rad_k, geom_pre, bin_pre, img_pre);
-                }
-                // a miss on the speculated buffers: back to the state after the last step served
-                check(gs_amr_set_step_state(reinterpret_cast<char*>(im.data_ptr()), (size_t)im.numel(), W, H,
-                                            sp.next - 1, stream),
-                      "amr speculation (level state)");
-                sp.clear();
-            } else if (foveaStep <= 1) {
-                sp.clear();  // a new frame (or a new step 1): nothing cached survives it
-            }
-            int amr_variant = 0;
-            check(gs_get_tuning("amr_variant", &amr_variant), "get_tuning");
-            if (foveaStep == 1 && t_spec_on && !interpolate_image && !debug && amr_variant == 4 && g.numel() &&
-                im.numel()) {
-                Tensor imgs = torch::empty({4, 3, H, W}, float_opts);
-                Tensor rads = torch::empty({4, P}, means3D_in.options().dtype(torch::kInt32));
-                rendered = gs_amr_accumulate_step(P, fptr(bg), W, H, fptr(colors), GSPLAT_AMD_AMR_STEPS_1_TO_4_SPLIT,
-                                                  reinterpret_cast<char*>(g.data_ptr()),
-                                                  b.numel() ? reinterpret_cast<char*>(b.data_ptr()) : nullptr,
-                                                  reinterpret_cast<char*>(im.data_ptr()), imgs.data_ptr<float>(),
-                                                  rads.data_ptr<int>(), 0, hint, stream);
-                check(rendered, "rasterize_gaussians (AMR, speculative steps 1..4)");
-                sp.g = g.data_ptr();
-                sp.b = b.numel() ? b.data_ptr() : nullptr;
-                sp.im = im.data_ptr();
-                sp.vg = version_of(g);
-                sp.vb = version_of(b);
-                sp.vim = version_of(im);
-                sp.bg = bg.data_ptr();
-                sp.vbg = version_of(background);
-                sp.col = colors.numel() ? colors.data_ptr() : nullptr;
-                sp.vcol = version_of(colors_in);
-                sp.W = W;
-                sp.H = H;
-                sp.P = P;
-                sp.K = rendered;
-                sp.stream = stream;
-                sp.images = imgs;
-                sp.radii = rads;
-                sp.next = 2;
-                return std::make_tuple(rendered, imgs[0], rads[0], geom_pre, bin_pre, img_pre);
-            }
-            rendered = gs_amr_rasterizer_forward_ex(
-                buf_of(geomBuffer), buf_of(binningBuffer), buf_of(imgBuffer), P, degree, M, fptr(bg), W, H,
-                fptr(means3D), fptr(sh), fptr(colors), fptr(opacity), fptr(scales), scale_modifier, fptr(rotations),
-                fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx, tan_fovy, prefiltered,
-                foveaStep, fptr(pre), g.numel() ? reinterpret_cast<char*>(g.data_ptr()) : nullptr,
-                b.numel() ? reinterpret_cast<char*>(b.data_ptr()) : nullptr,
-                im.numel() ? reinterpret_cast<char*>(im.data_ptr()) : nullptr, out_color.data_ptr<float>(),
-                radii.data_ptr<int>(), interpolate_image, debug, hint, stream);
-            check(rendered, "rasterize_gaussians (AMR)");
-        }
+    ForwardCall o;
+    o.geom = torch::empty({0}, byte_opts);
+    o.binning = torch::empty({0}, byte_opts);
+    o.image = torch::empty({0}, byte_opts);
+    if (P == 0) {
+        const Tensor zero_image = torch::zeros({3, H, W}, float_opts), no_radii = torch::zeros({0}, int_opts);
+        if (amr && foveaStep > 0) return std::make_tuple(0, zero_image, no_radii, geom_pre, bin_pre, img_pre);
+        return std::make_tuple(0, zero_image, no_radii, o.geom, o.binning, o.image);
     }
-    if (amr && foveaStep > 0)  // amr/rasterize_points.cu:182-190: hand the precomputed buffers back
-        return std::make_tuple(rendered, out_color, radii, geom_pre, bin_pre, img_pre);
-    return std::make_tuple(rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer);
+    o.bg = background.contiguous();
+    o.means3D = means3D_in.contiguous();
+    o.colors = colors_in.contiguous();
+    o.opacity = opacity_in.contiguous();
+    o.scales = scales_in.contiguous();
+    o.rotations = rotations_in.contiguous();
+    o.cov3D_precomp = cov3D_precomp_in.contiguous();
+    o.viewmatrix = viewmatrix_in.contiguous();
+    o.projmatrix = projmatrix_in.contiguous();
+    o.sh = sh_in.contiguous();
+    o.campos = campos_in.contiguous();
+    check_operands(o.means3D, P, o.bg, o.colors, o.opacity, o.scales, o.rotations, o.cov3D_precomp, o.viewmatrix,
+                   o.projmatrix, o.sh, o.campos);
+    o.P = P;
+    o.M = o.sh.size(0) != 0 ? (int)o.sh.size(1) : 0;
+    o.W = W;
+    o.H = H;
+    o.degree = degree;
+    o.scale_modifier = scale_modifier;
+    o.tan_fovx = tan_fovx;
+    o.tan_fovy = tan_fovy;
+    o.prefiltered = prefiltered;
+    o.debug = debug;
+    o.stream = stream_of(o.means3D);
+    // both forwards write every pixel (the AMR one zeros where it renders
+    // nothing) and all radii (the AMR steps >= 1 write their zero radii in
+    // the fovea-levels launch)
+    o.out_color = torch::empty({3, H, W}, float_opts);
+    o.radii = torch::empty({P}, int_opts);
+    if (!amr) return base_forward(o);
+    return amr_forward(o, background, colors_in, foveaStep, out_color_precomp_in, geom_pre, bin_pre, img_pre,
+                       interpolate_image);
 }
 
 // base/rasterize_points.cu:35-115
@@ -502,10 +561,66 @@ Tensor RasterizeGaussiansBackwardViewGrads(const Tensor& background, const Tenso
     return rec;
 }
 
-// Data-parallel stage 2: the per-Gaussian backward of V views at once (views
-// = [V, P * 10 + 40] records), summed over views; returns (dL_dmeans3D,
-// dL_dsh, dL_dopacity, dL_dscales, dL_drotations); densification statistics
-// accumulated in place when given (non-empty).
+// Data-parallel stage 2: the per-Gaussian backward of V views at once, summed
+// over views, in three forms that differ in how the views' rows and cameras
+// arrive.  What they share: the per-Gaussian operands (contiguous, checked),
+// the five outputs and the three densification statistics (accumulated in
+// place when given, i.e. non-empty), as the pointers the C entries take.
+struct MultiviewOperands {
+    int P, M;
+    Tensor means3D, sh, scales, rotations;
+    float *dL_dmeans3D, *dL_dsh, *dL_dopacity, *dL_dscales, *dL_drotations;
+    float *grad_norm_accum, *denom, *max_radii;  // null: no statistics
+    void* stream;
+};
+
+// caller_outputs: the outputs are the caller's full-size tensors, to be checked
+// (else the binding allocated them itself).
+MultiviewOperands multiview_operands(const Tensor& means3D_in, const Tensor& sh_in, const Tensor& scales_in,
+                                     const Tensor& rotations_in, bool caller_outputs, Tensor& dL_dmeans3D,
+                                     Tensor& dL_dsh, Tensor& dL_dopacity, Tensor& dL_dscales, Tensor& dL_drotations,
+                                     Tensor& grad_norm_accum, Tensor& denom, Tensor& max_radii) {
+    MultiviewOperands o;
+    const int P = (int)means3D_in.size(0);
+    const int M = sh_in.numel() != 0 ? (int)sh_in.size(1) : 0;
+    o.P = P;
+    o.M = M;
+    if (caller_outputs) {
+        for (const Tensor* t : {&dL_dmeans3D, &dL_dopacity, &dL_dscales, &dL_drotations})
+            TORCH_CHECK(t->is_contiguous() && t->size(0) == P && t->scalar_type() == torch::kFloat32,
+                        "outputs must be contiguous float32 [P, ...] tensors");
+        TORCH_CHECK(M == 0 || (dL_dsh.is_contiguous() && dL_dsh.numel() == (int64_t)P * M * 3),
+                    "dL_dsh must be [P, M, 3]");
+    }
+    const bool stats = grad_norm_accum.numel() != 0;
+    if (stats) {
+        for (const Tensor* t : {&grad_norm_accum, &denom, &max_radii}) {
+            TORCH_CHECK(t->numel() == P && t->is_contiguous() && t->is_cuda() && t->scalar_type() == torch::kFloat32,
+                        "statistics tensors must be contiguous float32 device tensors with P elements");
+        }
+    }
+    o.means3D = means3D_in.contiguous();
+    o.sh = sh_in.contiguous();
+    o.scales = scales_in.contiguous();
+    o.rotations = rotations_in.contiguous();
+    require_device(o.means3D, "means3D");
+    require_like(o.scales, o.means3D, "scales", 3LL * P);
+    require_like(o.rotations, o.means3D, "rotations", 4LL * P);
+    require_like(o.sh, o.means3D, "sh", (int64_t)P * M * 3);
+    o.dL_dmeans3D = fptr_mut(dL_dmeans3D);
+    o.dL_dsh = M ? fptr_mut(dL_dsh) : nullptr;
+    o.dL_dopacity = fptr_mut(dL_dopacity);
+    o.dL_dscales = fptr_mut(dL_dscales);
+    o.dL_drotations = fptr_mut(dL_drotations);
+    o.grad_norm_accum = stats ? grad_norm_accum.data_ptr<float>() : nullptr;
+    o.denom = stats ? denom.data_ptr<float>() : nullptr;
+    o.max_radii = stats ? max_radii.data_ptr<float>() : nullptr;
+    o.stream = P != 0 ? stream_of(o.means3D) : nullptr;
+    return o;
+}
+
+// views = [V, P * 10 + 40] packed view records; returns (dL_dmeans3D, dL_dsh,
+// dL_dopacity, dL_dscales, dL_drotations).
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> BackwardGaussiansMultiview(
     const Tensor& views_in, const Tensor& means3D_in, const Tensor& sh_in, const int degree, const Tensor& scales_in,
     const Tensor& rotations_in, const float scale_modifier, Tensor grad_norm_accum, Tensor denom,
@@ -522,35 +637,23 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> BackwardGaussiansMultiview(
     Tensor dL_dopacity = torch::empty({P, 1}, opts);
     Tensor dL_dscales = torch::empty({P, 3}, opts);
     Tensor dL_drotations = torch::empty({P, 4}, opts);
-    const bool stats = grad_norm_accum.numel() != 0;
-    if (stats) {
-        for (const Tensor* t : {&grad_norm_accum, &denom, &max_radii}) {
-            TORCH_CHECK(t->numel() == P && t->is_contiguous() && t->is_cuda() && t->scalar_type() == torch::kFloat32,
-                        "statistics tensors must be contiguous float32 device tensors with P elements");
-        }
-    }
+    const MultiviewOperands o =
+        multiview_operands(means3D_in, sh_in, scales_in, rotations_in, false, dL_dmeans3D, dL_dsh, dL_dopacity,
+                           dL_dscales, dL_drotations, grad_norm_accum, denom, max_radii);
     if (P != 0) {
-        const Tensor views = views_in.contiguous(), means3D = means3D_in.contiguous(), sh = sh_in.contiguous(),
-                     scales = scales_in.contiguous(), rotations = rotations_in.contiguous();
-        require_device(means3D, "means3D");
-        require_like(views, means3D, "views");
-        require_like(scales, means3D, "scales", 3LL * P);
-        require_like(rotations, means3D, "rotations", 4LL * P);
-        require_like(sh, means3D, "sh", (int64_t)P * M * 3);
-        check(gs_backward_gaussians_multiview(
-                  P, degree, M, V, fptr(views), fptr(means3D), fptr(sh), fptr(scales), fptr(rotations),
-                  scale_modifier, fptr_mut(dL_dmeans3D), fptr_mut(dL_dsh), fptr_mut(dL_dopacity), fptr_mut(dL_dscales),
-                  fptr_mut(dL_drotations), stats ? grad_norm_accum.data_ptr<float>() : nullptr,
-                  stats ? denom.data_ptr<float>() : nullptr, stats ? max_radii.data_ptr<float>() : nullptr,
-                  stream_of(means3D)),
+        const Tensor views = views_in.contiguous();
+        require_like(views, o.means3D, "views");
+        check(gs_backward_gaussians_multiview(P, degree, M, V, fptr(views), fptr(o.means3D), fptr(o.sh),
+                                              fptr(o.scales), fptr(o.rotations), scale_modifier, o.dL_dmeans3D,
+                                              o.dL_dsh, o.dL_dopacity, o.dL_dscales, o.dL_drotations,
+                                              o.grad_norm_accum, o.denom, o.max_radii, o.stream),
               "backward_gaussians_multiview");
     }
     return std::make_tuple(dL_dmeans3D, dL_dsh, dL_dopacity, dL_dscales, dL_drotations);
 }
 
-// Chunked stage 2: rows [V, count * 10] (view v's rows of Gaussians [g0,
-// g0 + count)), cams [V, 40]; writes that range of the caller's full-size
-// output tensors (and statistics, when non-empty).
+// Chunked: rows [V, count * 10] (view v's rows of Gaussians [g0, g0 + count)),
+// cams [V, 40]; writes that range of the caller's full-size output tensors.
 void BackwardGaussiansMultiviewRange(const Tensor& rows_in, const Tensor& cams_in, const int g0,
                                      const Tensor& means3D_in, const Tensor& sh_in, const int degree,
                                      const Tensor& scales_in, const Tensor& rotations_in, const float scale_modifier,
@@ -562,42 +665,24 @@ void BackwardGaussiansMultiviewRange(const Tensor& rows_in, const Tensor& cams_i
     const int count = (int)(rows_in.size(1) / 10);
     TORCH_CHECK(cams_in.dim() == 2 && cams_in.size(0) == V && cams_in.size(1) == 40, "cams must be [V, 40]");
     TORCH_CHECK(g0 >= 0 && g0 + count <= P, "Gaussian range out of bounds");
-    const int M = sh_in.numel() != 0 ? (int)sh_in.size(1) : 0;
-    for (const Tensor* t : {&dL_dmeans3D, &dL_dopacity, &dL_dscales, &dL_drotations})
-        TORCH_CHECK(t->is_contiguous() && t->size(0) == P && t->scalar_type() == torch::kFloat32,
-                    "outputs must be contiguous float32 [P, ...] tensors");
-    TORCH_CHECK(M == 0 || (dL_dsh.is_contiguous() && dL_dsh.numel() == (int64_t)P * M * 3), "dL_dsh must be [P, M, 3]");
-    const bool stats = grad_norm_accum.numel() != 0;
-    if (stats) {
-        for (const Tensor* t : {&grad_norm_accum, &denom, &max_radii}) {
-            TORCH_CHECK(t->numel() == P && t->is_contiguous() && t->is_cuda() && t->scalar_type() == torch::kFloat32,
-                        "statistics tensors must be contiguous float32 device tensors with P elements");
-        }
-    }
     const at::OptionalDeviceGuard guard(device_of(means3D_in));
+    const MultiviewOperands o =
+        multiview_operands(means3D_in, sh_in, scales_in, rotations_in, true, dL_dmeans3D, dL_dsh, dL_dopacity,
+                           dL_dscales, dL_drotations, grad_norm_accum, denom, max_radii);
     TORCH_CHECK(rows_in.stride(1) == 1 && cams_in.stride(1) == 1, "rows / cams rows must be contiguous");
-    const Tensor means3D = means3D_in.contiguous(), sh = sh_in.contiguous(), scales = scales_in.contiguous(),
-                 rotations = rotations_in.contiguous();
-    require_device(means3D, "means3D");
-    require_like(rows_in, means3D, "rows");
-    require_like(cams_in, means3D, "cams");
-    require_like(scales, means3D, "scales", 3LL * P);
-    require_like(rotations, means3D, "rotations", 4LL * P);
-    require_like(sh, means3D, "sh", (int64_t)P * M * 3);
+    require_like(rows_in, o.means3D, "rows");
+    require_like(cams_in, o.means3D, "cams");
     check(gs_backward_gaussians_multiview_range(
-              P, g0, count, degree, M, V, rows_in.data_ptr<float>(), (size_t)rows_in.stride(0), cams_in.data_ptr<float>(),
-              (size_t)cams_in.stride(0), fptr(means3D), fptr(sh), fptr(scales), fptr(rotations), scale_modifier,
-              fptr_mut(dL_dmeans3D), M ? fptr_mut(dL_dsh) : nullptr, fptr_mut(dL_dopacity), fptr_mut(dL_dscales),
-              fptr_mut(dL_drotations), stats ? grad_norm_accum.data_ptr<float>() : nullptr,
-              stats ? denom.data_ptr<float>() : nullptr, stats ? max_radii.data_ptr<float>() : nullptr,
-              stream_of(means3D)),
+              P, g0, count, degree, o.M, V, rows_in.data_ptr<float>(), (size_t)rows_in.stride(0),
+              cams_in.data_ptr<float>(), (size_t)cams_in.stride(0), fptr(o.means3D), fptr(o.sh), fptr(o.scales),
+              fptr(o.rotations), scale_modifier, o.dL_dmeans3D, o.dL_dsh, o.dL_dopacity, o.dL_dscales,
+              o.dL_drotations, o.grad_norm_accum, o.denom, o.max_radii, o.stream),
           "backward_gaussians_multiview_range");
 }
 
-// Stage 2 over separately stored views: rows[v] = view v's rows of Gaussians
-// [g0, g0 + count) (a contiguous [count * 10] slice), cams[v] = its camera
-// ([40]); views summed in list order.  Each all-gathered piece can stay in its
-// own [world, n] buffer.
+// Separately stored views: rows[v] = view v's rows of Gaussians [g0, g0 + count)
+// (a contiguous [count * 10] slice), cams[v] = its camera ([40]); views summed
+// in list order.  Each all-gathered piece can stay in its own [world, n] buffer.
 void BackwardGaussiansMultiviewViews(const std::vector<Tensor>& rows, const std::vector<Tensor>& cams, const int g0,
                                      const Tensor& means3D_in, const Tensor& sh_in, const int degree,
                                      const Tensor& scales_in, const Tensor& rotations_in, const float scale_modifier,
@@ -609,41 +694,24 @@ void BackwardGaussiansMultiviewViews(const std::vector<Tensor>& rows, const std:
     TORCH_CHECK(rows[0].dim() == 1 && rows[0].numel() % 10 == 0, "rows[v] must be a 1-D [count * 10] slice");
     const int count = (int)(rows[0].numel() / 10);
     TORCH_CHECK(g0 >= 0 && g0 + count <= P, "Gaussian range out of bounds");
-    const int M = sh_in.numel() != 0 ? (int)sh_in.size(1) : 0;
-    for (const Tensor* t : {&dL_dmeans3D, &dL_dopacity, &dL_dscales, &dL_drotations})
-        TORCH_CHECK(t->is_contiguous() && t->size(0) == P && t->scalar_type() == torch::kFloat32,
-                    "outputs must be contiguous float32 [P, ...] tensors");
-    TORCH_CHECK(M == 0 || (dL_dsh.is_contiguous() && dL_dsh.numel() == (int64_t)P * M * 3), "dL_dsh must be [P, M, 3]");
-    const bool stats = grad_norm_accum.numel() != 0;
-    if (stats) {
-        for (const Tensor* t : {&grad_norm_accum, &denom, &max_radii}) {
-            TORCH_CHECK(t->numel() == P && t->is_contiguous() && t->is_cuda() && t->scalar_type() == torch::kFloat32,
-                        "statistics tensors must be contiguous float32 device tensors with P elements");
-        }
-    }
     const at::OptionalDeviceGuard guard(device_of(means3D_in));
-    const Tensor means3D = means3D_in.contiguous(), sh = sh_in.contiguous(), scales = scales_in.contiguous(),
-                 rotations = rotations_in.contiguous();
-    require_device(means3D, "means3D");
+    const MultiviewOperands o =
+        multiview_operands(means3D_in, sh_in, scales_in, rotations_in, true, dL_dmeans3D, dL_dsh, dL_dopacity,
+                           dL_dscales, dL_drotations, grad_norm_accum, denom, max_radii);
     std::vector<const float*> rp(V), cp(V);
     for (int v = 0; v < V; v++) {
         TORCH_CHECK(rows[v].dim() == 1 && rows[v].numel() == (int64_t)count * 10 && rows[v].is_contiguous(),
                     "rows[v] must be contiguous [count * 10] slices of equal length");
         TORCH_CHECK(cams[v].dim() == 1 && cams[v].numel() == 40 && cams[v].is_contiguous(), "cams[v] must be [40]");
-        require_like(rows[v], means3D, "rows");
-        require_like(cams[v], means3D, "cams");
+        require_like(rows[v], o.means3D, "rows");
+        require_like(cams[v], o.means3D, "cams");
         rp[v] = rows[v].data_ptr<float>();
         cp[v] = cams[v].data_ptr<float>();
     }
-    require_like(scales, means3D, "scales", 3LL * P);
-    require_like(rotations, means3D, "rotations", 4LL * P);
-    require_like(sh, means3D, "sh", (int64_t)P * M * 3);
-    check(gs_backward_gaussians_multiview_views(
-              P, g0, count, degree, M, V, rp.data(), cp.data(), fptr(means3D), fptr(sh), fptr(scales),
-              fptr(rotations), scale_modifier, fptr_mut(dL_dmeans3D), M ? fptr_mut(dL_dsh) : nullptr,
-              fptr_mut(dL_dopacity), fptr_mut(dL_dscales), fptr_mut(dL_drotations),
-              stats ? grad_norm_accum.data_ptr<float>() : nullptr, stats ? denom.data_ptr<float>() : nullptr,
-              stats ? max_radii.data_ptr<float>() : nullptr, stream_of(means3D)),
+    check(gs_backward_gaussians_multiview_views(P, g0, count, degree, o.M, V, rp.data(), cp.data(), fptr(o.means3D),
+                                                fptr(o.sh), fptr(o.scales), fptr(o.rotations), scale_modifier,
+                                                o.dL_dmeans3D, o.dL_dsh, o.dL_dopacity, o.dL_dscales,
+                                                o.dL_drotations, o.grad_norm_accum, o.denom, o.max_radii, o.stream),
           "backward_gaussians_multiview_views");
 }
 

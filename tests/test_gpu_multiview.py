@@ -155,6 +155,55 @@ def test_multiview_more_than_64_views():
         assert torch.equal(a.reshape(-1), b.reshape(-1))
 
 
+def test_three_multiview_forms_agree_bit_for_bit():
+    """The packed-record binding, the chunked `_range` binding (two chunks
+    split at Gaussian 777, no multiple of any block size) and the per-view
+    `_views` binding run the same kernel over the same views in the same order
+    (gs_api.cpp multiview_impl): the five outputs and the three statistics are
+    bit-identical, with and without the statistics tensors."""
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
+    from gaussian_splatting_with_eye_tracking_amd import synthetic as S
+    P, W, H, split = 2000, 96, 80, 777
+    sc, cams = _views(P, W, H, (-6.0, 0.0, 7.0))
+    t = G.scene_tensors(sc)
+    records = []
+    for v, cam in enumerate(cams):
+        s = G.torch_settings(cam)
+        dpix = torch.from_numpy(S.make_cotangent(H, W, 70 + v)).cuda()
+        fwd = _forward(C, s, t)
+        records.append(DP.view_record(s, fwd[2], fwd[3], fwd[0], fwd[4], fwd[5], dpix))
+    views = torch.stack(records).contiguous()
+    V, R, M = len(cams), P * DP.VIEW_ROW, t["shs"].shape[1]
+    ops = (t["means3D"], t["shs"], 3, t["scales"], t["rotations"], 1.0)
+
+    def outputs():
+        return [torch.full(shape, float("nan"), device="cuda") for shape in ((P, 3), (P, M, 3), (P, 1), (P, 3), (P, 4))]
+
+    def statistics(on):  # (accumulated in place: a non-zero start shows a chunk that adds twice or not at all)
+        return [torch.full((P,), float(i + 1), device="cuda") if on else torch.empty(0, device="cuda") for i in range(3)]
+
+    for with_stats in (True, False):
+        st_packed, st_range, st_views = statistics(with_stats), statistics(with_stats), statistics(with_stats)
+        packed = C.backward_gaussians_multiview(views, *ops, *st_packed)
+        ranged = outputs()
+        for a, b in ((0, split), (split, P)):
+            C.backward_gaussians_multiview_range(views[:, a * DP.VIEW_ROW:b * DP.VIEW_ROW], views[:, R:], a, *ops,
+                                                 *ranged, *st_range)
+        per_view = outputs()
+        C.backward_gaussians_multiview_views([views[v, :R] for v in range(V)], [views[v, R:] for v in range(V)], 0,
+                                             *ops, *per_view, *st_views)
+        torch.cuda.synchronize()
+        for i, want in enumerate(packed):
+            assert torch.isfinite(want).all(), i
+            assert torch.equal(ranged[i], want), (with_stats, i)
+            assert torch.equal(per_view[i], want), (with_stats, i)
+        for i in range(3 if with_stats else 0):
+            assert torch.equal(st_range[i], st_packed[i]) and torch.equal(st_views[i], st_packed[i]), i
+        if with_stats:  # (the views did add to the gradient norms and the counts)
+            assert (st_packed[0] > 1.0).any() and (st_packed[1] > 2.0).any()
+
+
 @pytest.mark.parametrize("n_streams", [2, 3])
 def test_views_on_streams_match_one_stream(n_streams):
     """data_parallel.run_views_on_streams (config 5's step): the views'
