@@ -4,6 +4,6 @@
 unchanged."""
 from gaussian_splatting_with_eye_tracking_amd.rasterization import (  # noqa: F401
     GaussianRasterizationSettings, GaussianRasterizer, _RasterizeGaussians, cpu_deep_copy_tuple,
-    rasterize_gaussians, set_deterministic)
+    rasterize_gaussians, rasterize_gaussians_aux, set_deterministic)
 
 from . import _C  # noqa: F401,E402

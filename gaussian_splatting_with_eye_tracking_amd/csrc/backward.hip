@@ -42,6 +42,7 @@ constexpr int kNG = 9;      // gradient terms per (pixel, Gaussian)
 static_assert(kDetRow == kNG, "the deterministic backward's partial rows hold the nine terms");
 constexpr int kAccRow = 9;   // LDS accumulator row (floats; odd stride: 9 scalar stores per row)
 constexpr int kPPL = 4;      // pixels per lane: one wave64 covers the 16x16 tile (gs_blend.cuh mapping)
+static_assert(kAuxDz == kAccRow && kAuxDz < kGradRow, "the aux backward's tenth sum takes a spare float of the row");
 
 // One 16x16 tile per single-wave workgroup, 4 pixels per lane (lane l: column
 // l % 16 of the 4 row groups).  kSel (the default): the select-form visit
@@ -56,8 +57,14 @@ constexpr int kPPL = 4;      // pixels per lane: one wave64 covers the 16x16 til
 // each Gaussian's rows in a fixed order.  Every row below min(n,
 // max_contrib[tile]) is written (zeros where the default flush adds nothing),
 // the rows at or past it are never read.
+// kAux (the depth / alpha maps' backward, on the fallback form): depth and
+// alpha are two more blend channels with features (z, 1), background (0, 0)
+// and cotangents dL_ddepth / dL_dalpha (either may be null, as dL_dpixels
+// then: zeros) replayed in the same walk -- dL/dalpha of every pair gains
+// their terms, and a tenth per-Gaussian sum dL/dz = sum alpha T dL_ddepth
+// goes to float kAuxDz of the Gaussian's grad_accum row (LDS rows of 10).
 // (a template parameter, as kAMR: run-time branches cost the base kernel 12 %)
-template <bool kSel, bool kAMR = false, bool kOpT = false, bool kDet = false>
+template <bool kSel, bool kAMR = false, bool kOpT = false, bool kDet = false, bool kAux = false>
 __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     int W, int H, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ max_contrib,
     const uint32_t* __restrict__ point_list, const float2* __restrict__ means2D,
@@ -65,9 +72,12 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels, const float* __restrict__ bg,
     float* __restrict__ grad_accum, int cull, int gx, int amr_mode, const uint32_t* __restrict__ levels,
     const uint32_t* __restrict__ bucket_count, const uint32_t* __restrict__ bucket_list,
-    const uint32_t* __restrict__ hdr) {
+    const uint32_t* __restrict__ hdr, const float* __restrict__ depths, const float* __restrict__ dL_ddepth,
+    const float* __restrict__ dL_dalpha_map) {
 #pragma clang fp contract(fast)
     static_assert(!(kSel && kAMR), "the AMR backward is the fallback form");
+    static_assert(!kAux || (!kSel && !kAMR && !kDet), "the aux backward is the base fallback form");
+    constexpr int kRow = kAux ? kAccRow + 1 : kAccRow;  // LDS accumulator row of this form
     static_assert(!kDet || (!kSel && !kAMR), "the deterministic backward is the base fallback form");
     constexpr int kB = 64;  // Gaussians per LDS batch
     __shared__ uint32_t s_id[2][kB];  // double-buffered: the next batch's ids land while this one flushes
@@ -78,7 +88,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     // (b at a 16-B stride: one LDS address serves all three record reads)
     __shared__ float4 s_b[kB];
     // !kSel: per-Gaussian sums, one row per batch slot, flushed per batch
-    __shared__ float s_acc[kSel ? 1 : kB * kAccRow];
+    __shared__ float s_acc[kSel ? 1 : kB * kRow];
     __shared__ uint64_t s_bal[4];
     // kSel: the per-Gaussian sums are finished in groups of 7 Gaussians --
     // each visit parks its two transposed registers (16 column partials of
@@ -162,6 +172,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     // recurrences (backward.cu:500-507) feed into dL_dalpha, so each pixel
     // carries that one scalar instead of 2 x 3.
     float T[kPPL], nbg[kPPL], dpx[kPPL][3], acc_dot[kPPL];
+    float dax[kAux ? kPPL : 1][2];  // kAux: (dL_ddepth, dL_dalpha) of the pixel
     uint32_t last[kPPL];
     uint32_t wave_last = 0;
 #pragma unroll
@@ -172,7 +183,12 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
         last[k] = px.inside[k] ? n_contrib[pid] : 0u;
         wave_last = max(wave_last, last[k]);
 #pragma unroll
-        for (int c = 0; c < 3; c++) dpx[k][c] = px.inside[k] ? dL_dpixels[c * plane + pid] : 0.f;
+        for (int c = 0; c < 3; c++)
+            dpx[k][c] = (px.inside[k] && (!kAux || dL_dpixels)) ? dL_dpixels[c * plane + pid] : 0.f;
+        if constexpr (kAux) {
+            dax[k][0] = (px.inside[k] && dL_ddepth) ? dL_ddepth[pid] : 0.f;
+            dax[k][1] = (px.inside[k] && dL_dalpha_map) ? dL_dalpha_map[pid] : 0.f;
+        }
         // (-T_final / (1 - alpha)) * bg.dL_dpix = nbg * 1/(1 - alpha)
         nbg[k] = -Tf * (bg0 * dpx[k][0] + bg1 * dpx[k][1] + bg2 * dpx[k][2]);
         // kSel: the background term folded into the recurrence -- with
@@ -230,7 +246,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     const float ddely_dy = (float)(0.5 * H);
     const int comp = lane & 15;
     // !kSel flush: the accumulator-row entry each output component starts from
-    const int ia = comp < 3 ? comp : comp == 8 ? 3 : comp < 5 ? 4 : comp + 1;
+    const int ia = (kAux && comp == kAuxDz) ? kAuxDz : comp < 3 ? comp : comp == 8 ? 3 : comp < 5 ? 4 : comp + 1;
 
     // Software pipeline over the batches (vector-memory counters retire in
     // issue order, so issue order decides what each wait covers): the next
@@ -246,12 +262,14 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
     float2 nxy = make_float2(0.f, 0.f);
     float4 nco = make_float4(0.f, 0.f, 0.f, 0.f);
     float nrgb[3] = {0.f, 0.f, 0.f};
+    float nz = 0.f;  // kAux: the Gaussian's view-space depth
     if (tid < min(kB, m)) {
         nid = point_list[range.x + m - 1 - tid];
         if (use_codes) ncode = codes[range.x + m - 1 - tid];
         nxy = means2D[nid];
         nco = conic_opacity[nid];
         nrgb[0] = colors[3 * nid]; nrgb[1] = colors[3 * nid + 1]; nrgb[2] = colors[3 * nid + 2];
+        if constexpr (kAux) nz = depths[nid];
         s_id[0][tid] = nid;
     }
     // kSel staging reduce: lane (slot = lane / 9, value q = lane % 9) sums the
@@ -296,6 +314,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
             s_a[tid] = make_float4(xy.x, xy.y, nrgb[0], nrgb[1]);
             s_co[tid] = pc;
             s_b[tid].x = nrgb[2];
+            if constexpr (kAux) s_b[tid].y = nz;
             if constexpr (kSel)  // the reference's `power > 0` skip cannot fire (gs_blend.cuh)
                 fastg = splat_form_safe(pc, fabsf(xy.x - (float)ox), fabsf(xy.y - (float)oy)) &&
                         (!kOpT || (pc.w <= 0.99f && pc.w > 0.0f));
@@ -395,6 +414,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
             // fma(a, b, -0) / -0 + t fold to a plain v_mul / move instead of a
             // 3-operand fma with an inline 0)
             float c0 = -0.f, c1 = -0.f, c2 = -0.f, s0 = -0.f, s1 = -0.f, s2 = -0.f;
+            float c3 = 0.f;  // kAux: sum alpha T dL_ddepth (cf.w = z)
             bool any = false;
             if constexpr (kSel) {
                 // The select form: a rejected pixel takes alpha = G = 0, i.e.
@@ -464,7 +484,11 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
                     const float dchannel_dcolor = alpha * T[k];
                     // sum_ch (c - accum_rec) dL_dpix, with accum_rec . dL_dpix
                     // advanced by the reference's recurrence (backward.cu:500-507)
-                    const float c_dot = cf.x * dpx[k][0] + cf.y * dpx[k][1] + cf.z * dpx[k][2];
+                    float c_dot = cf.x * dpx[k][0] + cf.y * dpx[k][1] + cf.z * dpx[k][2];
+                    if constexpr (kAux) {  // the channels (z, 1)
+                        c_dot += cf.w * dax[k][0] + dax[k][1];
+                        c3 = __builtin_fmaf(dchannel_dcolor, dax[k][0], c3);
+                    }
                     // The reference advances accum_rec at the NEXT contributor from the
                     // stored (last_alpha, last_color); advancing it here with the same
                     // operands gives the same bits and needs no per-pixel "last" state.
@@ -505,12 +529,23 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
                 // full sums by transposition: 2 values per row leader + g8 in lane 63
                 float za, zb;
                 swap_sum9(g, za, zb);
+                if constexpr (kAux) {  // the tenth sum: the plain DPP tree, total in lane 63
+                    c3 = dpp_add<0x111, 0xf, true>(c3);   // row_shr:1
+                    c3 = dpp_add<0x112, 0xf, true>(c3);   // row_shr:2
+                    c3 = dpp_add<0x114, 0xf, true>(c3);   // row_shr:4
+                    c3 = dpp_add<0x118, 0xf, true>(c3);   // row_shr:8
+                    c3 = dpp_add<0x142, 0xa, false>(c3);  // row_bcast:15
+                    c3 = dpp_add<0x143, 0xc, false>(c3);  // row_bcast:31
+                }
                 if ((lane & 15) == 15) {
-                    float* row = &s_acc[j * kAccRow];
+                    float* row = &s_acc[j * kRow];
                     const int q = swap_sum_slot(lane >> 4);
                     row[q] = za;
                     row[4 + q] = zb;
-                    if (lane == 63) row[8] = g[8];
+                    if (lane == 63) {
+                        row[8] = g[8];
+                        if constexpr (kAux) row[kAuxDz] = c3;
+                    }
                 }
                 written |= 1ull << j;
             }
@@ -565,7 +600,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
                 todo &= todo - 1;
                 const float4 a4 = s_a[j];
                 const float2 xy = make_float2(a4.x, a4.y);
-                const float4 pc = s_co[j], cf = make_float4(a4.z, a4.w, s_b[j].x, 0.f);
+                const float4 pc = s_co[j], cf = make_float4(a4.z, a4.w, s_b[j].x, kAux ? s_b[j].y : 0.f);
                 visit(j, xy, pc, cf, T0{}, T0{}, S0{});
             }
         }
@@ -575,6 +610,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
             nxy = means2D[nid];
             nco = conic_opacity[nid];
             nrgb[0] = colors[3 * nid]; nrgb[1] = colors[3 * nid + 1]; nrgb[2] = colors[3 * nid + 2];
+            if constexpr (kAux) nz = depths[nid];
         }
         if constexpr (!kSel) {
             // Flush: 16 lanes per Gaussian row, 4 rows per wave instruction
@@ -590,12 +626,12 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(
                     if (r < cnt && comp < kNG && !wr)
                         grad_accum[(size_t)(range.x + (uint32_t)(top - 1 - r)) * kNG + comp] = 0.f;
                 }
-                const bool live = r < cnt && comp < kNG && wr;
+                const bool live = r < cnt && comp < kRow && wr;
                 if (live) {
                     // row sums (c0, c1, c2, s0, sx, sy, sxx, sxy, syy) -> the
                     // reference's nine terms: v = ka * row[ia] + kb * sy, with o and
                     // the conic from the staged log2(e)-scaled record
-                    const float* row0 = &s_acc[r * kAccRow];
+                    const float* row0 = &s_acc[r * kRow];
                     const float qa = row0[ia], qb = row0[5];
                     const float4 pc = s_co[r];
                     const float o = pc.w;
@@ -653,7 +689,7 @@ void launch_render_backward(int W, int H, const ImageView& img, const BinningVie
                        b.point_list, reinterpret_cast<const float2*>(g.means2D),                                   \
                        reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,    \
                        dL_dpix, bg, g.grad_accum, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list,       \
-                       g.hdr)
+                       g.hdr, nullptr, nullptr, nullptr)
     if (g_bwd_variant == 0) GS_BWD_LAUNCH(false);
     else GS_BWD_LAUNCH(true, false, true);
 #undef GS_BWD_LAUNCH
@@ -758,11 +794,52 @@ void launch_render_backward_deterministic(int W, int H, int P, int R, const Imag
     hipLaunchKernelGGL((render_bwd_kernel<false, false, false, true>), dim3(gx * gy), dim3(64), 0, s, W, H, img.ranges,
                        img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
                        reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
-                       dL_dpix, bg, partials, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr);
+                       dL_dpix, bg, partials, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr,
+                       nullptr, nullptr, nullptr);
     const unsigned groups = ((unsigned)P + 15u) / 16u;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(groups), dim3(256), 0, s, P, (uint32_t)R, (uint32_t)gx,
                        (uint32_t)gy, radii, reinterpret_cast<const float2*>(g.means2D), g.depths, g.tiles_touched,
                        img.ranges, img.max_contrib, b.point_list, partials, g.grad_accum, g.hdr, err_token);
+}
+
+// The blend backward with the depth and alpha maps' cotangents
+// (gs_rasterizer_backward_aux): render_bwd_kernel kAux, five channels in one
+// walk of the tile lists, ten sums per Gaussian into g.grad_accum.
+void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
+                                const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
+                                const float* dL_dalpha, hipStream_t s) {
+    const int gx = (W + 15) / 16, gy = (H + 15) / 16;
+    if (gx == 0 || gy == 0) return;
+    const DispatchEvents ev = take_dispatch_events();
+    hipExtLaunchKernelGGL((render_bwd_kernel<false, false, false, false, true>), dim3(gx * gy), dim3(64), 0, s,
+                          ev.start, ev.stop, 0, W, H, img.ranges, img.max_contrib, b.point_list,
+                          reinterpret_cast<const float2*>(g.means2D),
+                          reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
+                          dL_dpix, bg, g.grad_accum, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr,
+                          g.depths, dL_ddepth, dL_dalpha);
+}
+
+// The depth map's direct term on the means: z = V[2] x + V[6] y + V[10] z +
+// V[14] of the flat viewmatrix (transformPoint4x3), so dL_dmeans3D[i] +=
+// dL/dz_i (V[2], V[6], V[10]) with dL/dz_i the row's float kAuxDz.  Runs
+// after backward_gaussians_kernel, which wrote every dL_dmeans3D element.
+__global__ void __launch_bounds__(256) aux_depth_to_means_kernel(int P, const int* __restrict__ radii,
+                                                                 const float* __restrict__ grad_accum,
+                                                                 const float* __restrict__ viewmatrix,
+                                                                 float* __restrict__ dL_dmean3D) {
+    const int idx = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (idx >= P || radii[idx] <= 0) return;
+    const float dz = grad_accum[(size_t)idx * kGradRow + kAuxDz];
+    dL_dmean3D[3 * idx + 0] += dz * viewmatrix[2];
+    dL_dmean3D[3 * idx + 1] += dz * viewmatrix[6];
+    dL_dmean3D[3 * idx + 2] += dz * viewmatrix[10];
+}
+
+void launch_aux_depth_to_means(int P, const GeomView& g, const int* radii, const float* viewmatrix,
+                               float* dL_dmean3D, hipStream_t s) {
+    if (P <= 0) return;
+    hipLaunchKernelGGL(aux_depth_to_means_kernel, dim3(((unsigned)P + 255u) / 256u), dim3(256), 0, s, P, radii,
+                       g.grad_accum, viewmatrix, dL_dmean3D);
 }
 
 // The foveated (AMR) blend backward: 32-px tile ranges, one wave per
@@ -777,7 +854,8 @@ void launch_amr_render_backward(int W, int H, int mode, const ImageView& img, co
     hipLaunchKernelGGL((render_bwd_kernel<false, true>), dim3(4 * tgx * tgy), dim3(64), 0, s, W, H, img.ranges,
                        img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
                        reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
-                       dL_dpix, bg, g.grad_accum, g_cull, tgx, mode, img.levels, nullptr, nullptr, nullptr);
+                       dL_dpix, bg, g.grad_accum, g_cull, tgx, mode, img.levels, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       nullptr);
 }
 
 // (the per-Gaussian backward math: gs_bwd_math.cuh)

@@ -662,6 +662,48 @@ int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image
     });
 }
 
+// The same forward -- the same launches in the same order, so the image, the
+// radii and the three buffers are the plain call's bits -- followed by one
+// replay of the tile lists for the depth and alpha maps.
+int gs_rasterizer_forward_aux(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                              const float* background, int width, int height, const float* means3D, const float* shs,
+                              const float* colors_precomp, const float* opacities, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                              float tan_fovy, int prefiltered, float* out_color, int* radii, float* out_depth,
+                              float* out_alpha, int debug, void* stream) {
+    const ForwardIn in = forward_in(false, P, D, M, background, width, height, means3D, shs, colors_precomp, opacities,
+                                    scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                                    tan_fovx, tan_fovy, prefiltered);
+    return guarded([&]() -> int {
+        if (!out_depth || !out_alpha) throw GsError("gs_rasterizer_forward_aux: out_depth / out_alpha is NULL");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        if (P <= 0) {  // nothing blended: zero maps
+            const size_t N = (width > 0 && height > 0) ? (size_t)width * (size_t)height : 0;
+            if (N) {
+                GS_HIP(hipMemsetAsync(out_depth, 0, sizeof(float) * N, s));
+                GS_HIP(hipMemsetAsync(out_alpha, 0, sizeof(float) * N, s));
+            }
+            return 0;
+        }
+        Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
+        const float* feats = colors_precomp ? colors_precomp : r.g.rgb;
+        bool zeroed;
+        {
+            StageTimer _t(kRender, s, true);
+            const bool zero = in.fwd_zero;
+            zeroed = launch_render_forward(width, height, r.img, r.b, r.g, feats, background, out_color, s,
+                                           zero ? r.g.grad_accum : nullptr, zero ? (size_t)kGradRow * (size_t)P : 0,
+                                           reinterpret_cast<uint8_t*>(r.b.scratch));
+        }
+        if (zeroed) set_accum_clean(r.g.grad_accum, true);
+        stage_check(debug != 0, s, "render");
+        launch_render_forward_aux(width, height, r.img, r.b, r.g, out_depth, out_alpha, s);
+        stage_check(debug != 0, s, "render_aux");
+        return r.K;
+    });
+}
+
 namespace {
 // The deterministic backward's scratch: one row of kDetRow floats per sorted
 // instance (gs_backward_deterministic_scratch_bytes).
@@ -696,6 +738,10 @@ struct BackwardCall {
     char *geom_buffer = nullptr, *binning_buffer = nullptr, *img_buffer = nullptr;
     float* out_record = nullptr;
     DetScratch det;
+    // gs_rasterizer_backward_aux: the depth / alpha maps' cotangents (either
+    // may be null; dL_dpix too there)
+    bool aux = false;
+    const float *dL_ddepth = nullptr, *dL_dalpha = nullptr;
     int debug = 0;
     hipStream_t s = nullptr;
 };
@@ -752,6 +798,16 @@ int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
             StageTimer _t(kRenderBwd, s);
             launch_amr_render_backward(c.width, c.height, amr_mode, v.img, v.b, g, colors, c.background, c.dL_dpix, s);
         }
+    } else if (c.aux) {
+        // five channels in one walk, float atomics onto the zeroed rows (all
+        // kGradRow floats of a row are zeroed, float kAuxDz included; a second
+        // backward of one forward finds the flag taken and zeroes them itself)
+        zero_accum_unless_clean(g, a.P, s);
+        if (c.R > 0) {
+            StageTimer _t(kRenderBwd, s, true);
+            launch_render_backward_aux(c.width, c.height, v.img, v.b, g, colors, c.background, c.dL_dpix, c.dL_ddepth,
+                                       c.dL_dalpha, s);
+        }
     } else {
         blend_backward(c.det, c.width, c.height, a.P, c.R, v.img, v.b, g, a.radii, colors, c.background, c.dL_dpix,
                        c.debug, s);
@@ -766,6 +822,10 @@ int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
     a.hdr = g.hdr;
     { StageTimer _t(kBwdGauss, s); launch_backward_gaussians(a, g, s); }
     stage_check(c.debug != 0, s, "preprocess_backward");
+    if (c.aux && c.dL_ddepth && c.R > 0) {  // the depth map's direct term on the means
+        launch_aux_depth_to_means(a.P, g, a.radii, a.viewmatrix, a.dL_dmean3D, s);
+        stage_check(c.debug != 0, s, "aux_depth_to_means");
+    }
     return 0;
 }
 
@@ -864,6 +924,33 @@ int gs_rasterizer_backward(int P, int D, int M, int R, const float* background, 
                                        tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
                                        dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                                        dL_dscale, dL_drot, debug, stream);
+        return rasterizer_backward_impl(0, c);
+    });
+}
+
+int gs_rasterizer_backward_aux(int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp,
+                               const float* scales, float scale_modifier, const float* rotations,
+                               const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                               const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                               char* geom_buffer, char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                               const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic,
+                               float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                               float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream) {
+    return guarded([&]() -> int {
+        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                       dL_dscale, dL_drot, debug, stream);
+        // no aux cotangent: the plain backward, unchanged
+        if (!dL_ddepth && !dL_dalpha) {
+            if (!dL_dpix && P > 0) throw GsError("gs_rasterizer_backward_aux: every cotangent is NULL");
+            return rasterizer_backward_impl(0, c);
+        }
+        c.aux = true;
+        c.dL_ddepth = dL_ddepth;
+        c.dL_dalpha = dL_dalpha;
         return rasterizer_backward_impl(0, c);
     });
 }

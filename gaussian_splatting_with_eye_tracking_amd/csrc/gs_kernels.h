@@ -105,6 +105,21 @@ void launch_reconstruct_keys(int T, const ImageView& img, const BinningView& b, 
 bool launch_render_forward(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                            const float* features, const float* bg, float* out_color, hipStream_t s,
                            float* zero_rows = nullptr, size_t zero_floats = 0, uint8_t* hit_codes = nullptr);
+// The depth / alpha maps of the forward just rendered into img (its n_contrib
+// and the sorted lists): out_depth = sum z alpha T, out_alpha = sum alpha T,
+// [H][W] each, every pixel written (render.hip render_aux_fwd_kernel).
+void launch_render_forward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
+                               float* out_depth, float* out_alpha, hipStream_t s);
+// Their backward: the blend backward over five channels (colour, z, 1) into
+// g.grad_accum -- floats 0..8 the totals of the nine sums, float kAuxDz
+// dL/dz (backward.hip render_bwd_kernel kAux).  Any cotangent may be null.
+void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
+                                const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
+                                const float* dL_dalpha, hipStream_t s);
+// dL_dmean3D += dL/dz (V[2], V[6], V[10]) for the visible Gaussians, after
+// launch_backward_gaussians has written dL_dmean3D.
+void launch_aux_depth_to_means(int P, const GeomView& g, const int* radii, const float* viewmatrix,
+                               float* dL_dmean3D, hipStream_t s);
 // Tuning knobs (gs_set_tuning): the default or one fallback each.
 void set_forward_variant(int v);
 void set_backward_variant(int v);

@@ -32,6 +32,10 @@ constexpr size_t kAlign = 256;
 // more bytes: 390 MB each per launch at config 4)
 constexpr int kGradRow = 12;
 static_assert(kGradRow == GSPLAT_AMD_GRAD_ROW, "the public layout constant");
+// float of the row that takes the aux backward's tenth sum, dL/dz of the
+// Gaussian's view-space depth (gs_rasterizer_backward_aux); floats 0..8 are
+// the nine blend sums, 10 and 11 stay spare
+constexpr int kAuxDz = 9;
 
 // Header words (geom buffer, device side).
 enum HdrWord : int {

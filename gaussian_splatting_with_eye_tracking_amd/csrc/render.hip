@@ -163,6 +163,118 @@ bool launch_render_forward(int W, int H, const ImageView& img, const BinningView
     return zero_n4 > 0;
 }
 
+// ------------------------------------------------- depth and alpha maps ---
+// gs_rasterizer_forward_aux: depth = sum z_i alpha_i T_i and alpha = sum
+// alpha_i T_i over exactly the colour blend's contributors, as a replay
+// behind the unchanged colour forward (whose image and buffers are therefore
+// the plain call's bits): a pixel's contributors are the entries below its
+// n_contrib that pass the `power > 0` and `alpha < 1/255` skips -- the T <
+// 1e-4 stop is already in n_contrib -- with alpha from the colour blend's own
+// expressions (splat_p2 / splat_exp), as the backward replays them.  One
+// wave64 per 16x16 tile, 4 pixels per lane (the backward's geometry), LDS
+// batches of 64 entries (x, y, z + the scaled conic), the row-group cull and
+// each row group's max n_contrib as wave-uniform skips.  Every pixel of the
+// image is written (zeros where nothing contributes).
+__global__ void __launch_bounds__(64) render_aux_fwd_kernel(int W, int H, const uint32_t* __restrict__ ranges,
+                                                            const uint32_t* __restrict__ point_list,
+                                                            const float2* __restrict__ means2D,
+                                                            const float4* __restrict__ conic_opacity,
+                                                            const float* __restrict__ depths,
+                                                            const uint32_t* __restrict__ n_contrib,
+                                                            float* __restrict__ out_depth,
+                                                            float* __restrict__ out_alpha, int cull, int gx) {
+    constexpr int kB = 64, kPPL = 4;
+    __shared__ float4 s_a[kB];  // (x, y, z, -)
+    __shared__ float4 s_co[kB];
+    __shared__ uint64_t s_bal[4];
+    const int lane = (int)threadIdx.x;
+    const int tile = xcd_block_tile((int)blockIdx.x, gx, (int)(gridDim.x / gx));
+    const uint32_t ox = (uint32_t)(tile % gx) * 16, oy = (uint32_t)(tile / gx) * 16;
+    const PixelSetT<kPPL> px = make_pixels_t<kPPL, 1>(W, H, ox, oy, 1);
+    const uint2 range = reinterpret_cast<const uint2*>(ranges)[tile];
+    const int n = (int)(range.y - range.x);
+    uint32_t last[kPPL];
+    int group_last[kPPL];
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < kPPL; k++) {
+        last[k] = px.inside[k] ? n_contrib[px.pid[k]] : 0u;
+        group_last[k] = __builtin_amdgcn_readfirstlane((int)wave_max_u32(last[k]));
+        m = max(m, group_last[k]);
+    }
+    m = min(m, n);  // entries at or past the tile's max n_contrib: no pixel's
+    float T[kPPL], D[kPPL], A[kPPL];
+#pragma unroll
+    for (int k = 0; k < kPPL; k++) {
+        T[k] = 1.0f;
+        D[k] = A[k] = 0.0f;
+    }
+    for (int b0 = 0; b0 < m; b0 += kB) {
+        const int cnt = min(kB, m - b0);
+        __syncthreads();  // single-wave workgroup: LDS fence only
+        uint32_t gm = 0;
+        if (lane < cnt) {
+            const uint32_t id = point_list[range.x + b0 + lane];
+            const float2 xy = means2D[id];
+            const float4 co = conic_opacity[id];
+            s_a[lane] = make_float4(xy.x, xy.y, depths[id], 0.f);
+            s_co[lane] = splat_coef(co);
+            gm = cull ? splat_group_mask(xy, co, (float)ox, (float)oy, 1.0f) : 0xfu;
+        }
+        publish_group_masks<1>(gm, s_bal);
+        __syncthreads();
+        uint64_t mk[kPPL];
+        uint64_t todo = 0;
+#pragma unroll
+        for (int k = 0; k < kPPL; k++) {
+            // slots j with entry b0 + j < group_last[k]
+            const int jk = group_last[k] - b0;
+            const uint64_t gcut = jk >= 64 ? ~0ull : (jk <= 0 ? 0ull : (1ull << jk) - 1ull);
+            mk[k] = uniform_u64(s_bal[k]) & gcut;
+            todo |= mk[k];
+        }
+        while (todo) {
+            const int j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const float4 a4 = s_a[j];
+            const float4 pc = s_co[j];
+            const uint32_t entry = (uint32_t)(b0 + j);
+            const float dx = a4.x - px.x;
+            const float pa = (pc.x * dx) * dx, pb = pc.y * dx;  // the lane's pixels share x
+#pragma unroll
+            for (int k = 0; k < kPPL; k++) {
+                if (!((mk[k] >> j) & 1ull)) continue;  // wave-uniform
+                const float dy = a4.y - px.y[k];
+                const float p2 = splat_p2(pa, pb, dy, pc);  // the colour blend's bits
+                const float alpha = fminf(0.99f, pc.w * splat_exp(p2));
+                const bool ok = entry < last[k] && !(p2 > 0.0f) && !(alpha < 1.0f / 255.0f);
+                if (!ok) continue;
+                const float w = alpha * T[k];
+                D[k] = __builtin_fmaf(a4.z, w, D[k]);
+                A[k] += w;
+                T[k] = T[k] * (1.0f - alpha);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kPPL; k++) {
+        if (!px.inside[k]) continue;
+        out_depth[px.pid[k]] = D[k];
+        out_alpha[px.pid[k]] = A[k];
+    }
+}
+
+void launch_render_forward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
+                               float* out_depth, float* out_alpha, hipStream_t s) {
+    const int gx = (W + 15) / 16, gy = (H + 15) / 16;
+    if (gx == 0 || gy == 0) return;
+    const DispatchEvents ev = take_dispatch_events();
+    hipExtLaunchKernelGGL(render_aux_fwd_kernel, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0, W, H, img.ranges,
+                          b.point_list, reinterpret_cast<const float2*>(g.means2D),
+                          reinterpret_cast<const float4*>(g.conic_opacity), g.depths, img.n_contrib, out_depth,
+                          out_alpha, g_cull, gx);
+}
+
 // ------------------------------------------------------------------- AMR ---
 // amr/cr/forward.cu:313-339: sub-lattice offset -> AMR round
 __device__ __forceinline__ uint32_t amr_round(uint32_t ox, uint32_t oy) {

@@ -181,6 +181,20 @@ Forward6 base_forward(ForwardCall& o) {
     return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
 }
 
+// The base forward with the depth and alpha maps ([1, H, W] each, in `maps`).
+Forward6 base_forward_aux(ForwardCall& o, std::pair<Tensor, Tensor>& maps) {
+    maps.first = torch::empty({1, o.H, o.W}, o.out_color.options());
+    maps.second = torch::empty({1, o.H, o.W}, o.out_color.options());
+    const int rendered = gs_rasterizer_forward_aux(
+        buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
+        fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
+        fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
+        o.prefiltered, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(), maps.first.data_ptr<float>(),
+        maps.second.data_ptr<float>(), o.debug, o.stream);
+    check(rendered, "rasterize_gaussians_aux");
+    return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
+}
+
 // Step `step` from the cache, or nothing: a miss.  A miss on the speculated
 // buffers sets their level state back to that after the last step served.
 std::optional<Forward6> spec_serve(const SpecKey& key, int step, bool plain, const Tensor& g, const Tensor& b,
@@ -253,7 +267,8 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
                         const Tensor& projmatrix_in, float tan_fovx, float tan_fovy, int image_height, int image_width,
                         const Tensor& sh_in, int degree, const Tensor& campos_in, bool prefiltered, int foveaStep,
                         const Tensor& out_color_precomp_in, const Tensor& geom_pre, const Tensor& bin_pre,
-                        const Tensor& img_pre, bool interpolate_image, bool debug) {
+                        const Tensor& img_pre, bool interpolate_image, bool debug,
+                        std::pair<Tensor, Tensor>* aux_maps = nullptr) {
     if (means3D_in.ndimension() != 2 || means3D_in.size(1) != 3) {
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     }
@@ -271,6 +286,7 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
     o.image = torch::empty({0}, byte_opts);
     if (P == 0) {
         const Tensor zero_image = torch::zeros({3, H, W}, float_opts), no_radii = torch::zeros({0}, int_opts);
+        if (aux_maps) *aux_maps = {torch::zeros({1, H, W}, float_opts), torch::zeros({1, H, W}, float_opts)};
         if (amr && foveaStep > 0) return std::make_tuple(0, zero_image, no_radii, geom_pre, bin_pre, img_pre);
         return std::make_tuple(0, zero_image, no_radii, o.geom, o.binning, o.image);
     }
@@ -303,6 +319,7 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
     // the fovea-levels launch)
     o.out_color = torch::empty({3, H, W}, float_opts);
     o.radii = torch::empty({P}, int_opts);
+    if (!amr && aux_maps) return base_forward_aux(o, *aux_maps);
     if (!amr) return base_forward(o);
     return amr_forward(o, background, colors_in, foveaStep, out_color_precomp_in, geom_pre, bin_pre, img_pre,
                        interpolate_image);
@@ -320,6 +337,23 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> RasterizeGaussians(
     return rasterize_impl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                           cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
                           degree, campos, prefiltered, -1, e, e, e, e, false, debug);
+}
+
+// RasterizeGaussians plus the depth and alpha maps:
+// (K, color, depth, alpha, radii, geom, binning, img).
+std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> RasterizeGaussiansAux(
+    const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity,
+    const Tensor& scales, const Tensor& rotations, const float scale_modifier, const Tensor& cov3D_precomp,
+    const Tensor& viewmatrix, const Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+    const int image_height, const int image_width, const Tensor& sh, const int degree, const Tensor& campos,
+    const bool prefiltered, const bool debug) {
+    auto e = torch::empty({0});
+    std::pair<Tensor, Tensor> maps;
+    Forward6 f = rasterize_impl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                                cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
+                                sh, degree, campos, prefiltered, -1, e, e, e, e, false, debug, &maps);
+    return std::make_tuple(std::get<0>(f), std::get<1>(f), maps.first, maps.second, std::get<2>(f), std::get<3>(f),
+                           std::get<4>(f), std::get<5>(f));
 }
 
 // amr/rasterize_points.cu:65-202
@@ -385,7 +419,10 @@ Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, co
                     const Tensor& viewmatrix_in, const Tensor& projmatrix_in, const float tan_fovx,
                     const float tan_fovy, const Tensor& dL_dout_color_in, const Tensor& sh_in, const int degree,
                     const Tensor& campos_in, const Tensor& geomBuffer, const int R, const Tensor& binningBuffer,
-                    const Tensor& imageBuffer, const bool debug, const bool lean) {
+                    const Tensor& imageBuffer, const bool debug, const bool lean,
+                    const Tensor* dL_ddepth_in = nullptr, const Tensor* dL_dalpha_in = nullptr) {
+    // (the aux binding: either map's cotangent, [1, H, W], or an empty tensor)
+    const bool aux = dL_ddepth_in && dL_dalpha_in && (dL_ddepth_in->numel() != 0 || dL_dalpha_in->numel() != 0);
     const int P = (int)means3D_in.size(0);
     const int H = (int)dL_dout_color_in.size(1);
     const int W = (int)dL_dout_color_in.size(2);
@@ -424,7 +461,25 @@ Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, co
         for (const Tensor* bt : {&geomBuffer, &binningBuffer, &imageBuffer})
             require_like(*bt, means3D, "geometry / binning / image buffer", -1, torch::kByte);
         int rc;
-        if (amr_step == 0 && t_det_backward) {
+        if (aux) {
+            TORCH_CHECK(amr_step == 0, "the AMR backward takes no depth / alpha cotangents");
+            TORCH_CHECK(!t_det_backward,
+                        "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
+                        "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
+                        "for this call");
+            const Tensor dd = dL_ddepth_in->contiguous(), da = dL_dalpha_in->contiguous();
+            if (dd.numel()) require_like(dd, means3D, "dL_ddepth", (int64_t)H * W);
+            if (da.numel()) require_like(da, means3D, "dL_dalpha", (int64_t)H * W);
+            rc = gs_rasterizer_backward_aux(
+                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
+                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
+                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
+                fptr(dL_dout), fptr(dd), fptr(da), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
+                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
+                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
+                fptr_mut(dL_drotations), debug, stream_of(means3D));
+        } else if (amr_step == 0 && t_det_backward) {
             Tensor scratch = det_scratch(P, R, means3D);
             rc = gs_rasterizer_backward_deterministic(
                 P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
@@ -490,6 +545,25 @@ Grads8 RasterizeGaussiansBackwardLean(const Tensor& background, const Tensor& me
     return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                         geomBuffer, R, binningBuffer, imageBuffer, debug, true);
+}
+
+// The backward of rasterize_gaussians_aux: the lean binding's arguments with
+// dL_ddepth / dL_dalpha ([1, H, W], or empty: absent) after dL_dout_color
+// (which is [3, H, W] always: it carries H and W; zeros when the colour took
+// no part).  With both empty it is rasterize_gaussians_backward (kLean: _lean,
+// for the autograd wrapper).
+template <bool kLean>
+Grads8 RasterizeGaussiansBackwardAux(const Tensor& background, const Tensor& means3D, const Tensor& radii,
+                                     const Tensor& colors, const Tensor& scales, const Tensor& rotations,
+                                     const float scale_modifier, const Tensor& cov3D_precomp,
+                                     const Tensor& viewmatrix, const Tensor& projmatrix, const float tan_fovx,
+                                     const float tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_ddepth,
+                                     const Tensor& dL_dalpha, const Tensor& sh, const int degree,
+                                     const Tensor& campos, const Tensor& geomBuffer, const int R,
+                                     const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug) {
+    return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
+                        geomBuffer, R, binningBuffer, imageBuffer, debug, kLean, &dL_ddepth, &dL_dalpha);
 }
 
 // The AMR backward (an extension: the reference's is unreachable): the
@@ -1044,6 +1118,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
     m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
+    m.def("rasterize_gaussians_aux", &RasterizeGaussiansAux);
+    m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux<false>);
+    m.def("rasterize_gaussians_backward_aux_lean", &RasterizeGaussiansBackwardAux<true>);
     m.def("amr_rasterize_gaussians_backward", &AmrRasterizeGaussiansBackward);
     m.def("set_deterministic_backward", [](bool on) { t_det_backward = on; });
     m.def("get_deterministic_backward", []() { return t_det_backward; });

@@ -35,6 +35,18 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      cov3Ds_precomp, raster_settings)
 
 
+def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                            raster_settings):
+    """``rasterize_gaussians`` plus the differentiable depth and alpha maps:
+    ``(color [3,H,W], radii [P], depth [1,H,W], alpha [1,H,W])`` with
+    ``depth = sum z_i alpha_i T_i`` (view-space z, no background term, NOT
+    normalised: divide by ``alpha`` yourself) and ``alpha = sum alpha_i T_i``
+    over the colour blend's contributors (INTEGRATION.md "Depth and alpha
+    maps").  ``color`` and ``radii`` are the plain call's bits."""
+    return _RasterizeGaussiansAux.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                        cov3Ds_precomp, raster_settings)
+
+
 def _call(fn, args, debug: bool, dump: str, what: str):
     """debug mode: snapshot the arguments and re-raise (base/.../__init__.py:83-90)."""
     if not debug:
@@ -151,6 +163,72 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grad_rotations, grad_cov3Ds_precomp, None)
 
 
+class _RasterizeGaussiansAux(torch.autograd.Function):
+    """_RasterizeGaussians with the depth and alpha maps as two more
+    differentiable outputs.  A backward that got neither map's cotangent is
+    the plain lean backward; one that got either has no deterministic form
+    and raises under the deterministic mode rather than use atomics."""
+
+    @classmethod
+    def apply(cls, *args):
+        hinted = _hint_forward_only(args[:8])
+        try:
+            return super().apply(*args)
+        finally:
+            _clear_hint(hinted)
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        s = raster_settings
+        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+                s.campos, s.prefiltered, s.debug)
+        num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer = _call(
+            _C.rasterize_gaussians_aux, args, s.debug, "snapshot_fw.dump", "forward")
+        ctx.raster_settings = s
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                              binningBuffer, imgBuffer)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(radii)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
+        if grad_out_color is None and grad_depth is None and grad_alpha is None:
+            return (None,) * 9
+        s = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
+         imgBuffer) = ctx.saved_tensors
+        aux = grad_depth is not None or grad_alpha is not None
+        if aux and deterministic_requested():
+            raise RuntimeError(
+                "rasterize_gaussians_aux: the deterministic backward has no form that takes depth / alpha "
+                "cotangents (a deterministic aux backward is not built); call set_deterministic(False) or keep "
+                "the depth and alpha maps out of the loss")
+        if grad_out_color is None:  # (the native call takes H and W from it)
+            grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=means3D.dtype,
+                                         device=means3D.device)
+        head = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color)
+        tail = (sh, s.sh_degree, s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
+        with _DeterministicScope():
+            if aux:
+                none = grad_out_color.new_empty(0)
+                args = head + (none if grad_depth is None else grad_depth,
+                               none if grad_alpha is None else grad_alpha) + tail
+                grads = _call(_C.rasterize_gaussians_backward_aux_lean, args, s.debug, "snapshot_bw.dump",
+                              "backward")
+            else:
+                grads = _call(_C.rasterize_gaussians_backward_lean, head + tail, s.debug, "snapshot_bw.dump",
+                              "backward")
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+         grad_scales, grad_rotations) = grads
+        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
+                grad_rotations, grad_cov3Ds_precomp, None)
+
+
 class GaussianRasterizationSettings(NamedTuple):
     image_height: int
     image_width: int
@@ -191,8 +269,10 @@ class GaussianRasterizer(nn.Module):
         return visible
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_aux=False):
+        """The reference's ``(color, radii)``; with ``return_aux=True`` (an
+        extension) ``(color, radii, depth, alpha)`` -- rasterize_gaussians_aux."""
         _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        return rasterize_gaussians(means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities,
-                                   _or_empty(scales), _or_empty(rotations), _or_empty(cov3D_precomp),
-                                   self.raster_settings)
+        fn = rasterize_gaussians_aux if return_aux else rasterize_gaussians
+        return fn(means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities, _or_empty(scales),
+                  _or_empty(rotations), _or_empty(cov3D_precomp), self.raster_settings)

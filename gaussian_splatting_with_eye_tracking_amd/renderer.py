@@ -56,13 +56,21 @@ def _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_c
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           starter=None, ender=None):
-    """gaussian_renderer/__init__.py:18-113."""
+           starter=None, ender=None, return_aux=False):
+    """gaussian_renderer/__init__.py:18-113.  ``return_aux=True`` (an
+    extension) adds ``"depth"`` and ``"alpha"``: the differentiable [1, H, W]
+    maps of ``rasterization.rasterize_gaussians_aux`` (depth not normalised)."""
     pts, st, op = _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)
     rasterizer = GaussianRasterizer(raster_settings=st)
     if starter is not None:
         starter.record()
-    image, radii = rasterizer(means2D=pts, **op)
+    if return_aux:
+        image, radii, depth, alpha = rasterizer(means2D=pts, return_aux=True, **op)
+    else:
+        image, radii = rasterizer(means2D=pts, **op)
     if ender is not None:
         ender.record()
-    return {"render": image, "viewspace_points": pts, "visibility_filter": radii > 0, "radii": radii}
+    out = {"render": image, "viewspace_points": pts, "visibility_filter": radii > 0, "radii": radii}
+    if return_aux:
+        out["depth"], out["alpha"] = depth, alpha
+    return out

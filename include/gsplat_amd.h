@@ -85,6 +85,57 @@ int gs_rasterizer_backward(int P, int D, int M, int R, const float* background, 
                            float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
                            float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream);
 
+/* Differentiable depth and alpha maps (no reference counterpart: the
+ * reference returns the colour image and the radii only).  Base rasterizer
+ * only; an addition at ABI version 7: no layout and no existing entry changed.
+ *
+ * gs_rasterizer_forward_aux takes gs_rasterizer_forward's arguments plus two
+ * float [height][width] outputs, summed over exactly the contributors of the
+ * colour blend (its power > 0 and alpha < 1/255 skips, its T < 1e-4 stop):
+ *   out_depth = sum_i z_i alpha_i T_i, z_i the view-space z of Gaussian i's
+ *               mean; NO background term and NOT normalised -- divide by
+ *               out_alpha yourself for an expected depth;
+ *   out_alpha = sum_i alpha_i T_i (= 1 - final T up to rounding).
+ * Both must be non-NULL; every pixel is written (P <= 0: zeros).  out_color,
+ * radii and the three buffers are bit-identical to gs_rasterizer_forward's on
+ * the same inputs, and either backward may follow on them.
+ *
+ * gs_rasterizer_backward_aux takes gs_rasterizer_backward's arguments plus
+ * the maps' cotangents dL_ddepth / dL_dalpha ([height][width]); each of the
+ * three cotangents may be NULL (zeros).  Depth and alpha are blended as two
+ * more channels with features (z_i, 1) and background (0, 0) in the same walk
+ * of the tile lists, so dL_dmean2D / dL_dconic / dL_dopacity and everything
+ * derived from them are the totals, and dL_dmean3D also carries the depth's
+ * direct term dL/dz_i * (V[2], V[6], V[10]) of the flat viewmatrix.  With
+ * both aux cotangents NULL the call IS gs_rasterizer_backward.  Usage:
+ *
+ *   K = gs_rasterizer_forward_aux(geom, bin, img, P, D, M, bg, W, H, ...,
+ *                                 color, radii, depth, alpha, 0, stream);
+ *   gs_rasterizer_backward_aux(P, D, M, K, bg, W, H, ..., geom_ptr, bin_ptr,
+ *                              img_ptr, dL_dcolor_img, dL_ddepth, dL_dalpha,
+ *                              dL_dmean2D, ..., 0, stream);
+ *
+ * The per-Gaussian sum dL/dz_i is accumulated in float 9 of the Gaussian's
+ * grad_accum row (floats 0..8 hold the nine blend sums, 10 and 11 stay
+ * spare).  Float atomics, as gs_rasterizer_backward: there is no
+ * deterministic form. */
+int gs_rasterizer_forward_aux(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                              const float* background, int width, int height, const float* means3D, const float* shs,
+                              const float* colors_precomp, const float* opacities, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                              const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                              float tan_fovy, int prefiltered, float* out_color, int* radii, float* out_depth,
+                              float* out_alpha, int debug, void* stream);
+int gs_rasterizer_backward_aux(int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp,
+                               const float* scales, float scale_modifier, const float* rotations,
+                               const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                               const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                               char* geom_buffer, char* binning_buffer, char* img_buffer, const float* dL_dpix,
+                               const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D, float* dL_dconic,
+                               float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                               float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream);
+
 /* Data-parallel training (no reference counterpart: the
  * reference trains one view per step on one GPU, train.py:67-125).
  *

@@ -1,0 +1,93 @@
+"""The reference of the depth / alpha maps and their backward, composed from
+the unchanged oracle (which blends arbitrary precomputed colours):
+
+* forward: one oracle forward for the view-space depths, a second one with
+  ``colors_precomp = (z, 1, 0)`` and a zero background -- channel 0 is the
+  depth map ``sum z alpha T``, channel 1 the alpha map ``sum alpha T``;
+* backward: the oracle backward of that second forward with the cotangent
+  ``(dL_ddepth, dL_dalpha, 0)``, plus ``dL_dcolors[:, 0] * V[:3, 2]`` on
+  ``dL_dmeans3D`` (z = m . V[:3, 2] + V[3, 2] in the row-vector convention),
+  plus the ordinary colour backward;
+* allowances: the backward is linear in the cotangent, so the two passes'
+  ``oracle.grad_allowance`` add, with ``|V[:3, 2]|`` times the aux pass's
+  ``dL_dcolors[:, 0]`` allowance on ``dL_dmeans3D``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+import oracle as O
+
+SUMMED = ("dL_dmeans3D", "dL_dmeans2D", "dL_dopacity", "dL_dcov3D", "dL_dscales", "dL_drotations", "dL_dconic")
+COLOUR_ONLY = ("dL_dcolors", "dL_dsh")
+
+
+def aux_features(depths) -> np.ndarray:
+    z = np.asarray(depths, np.float32).reshape(-1)
+    return np.ascontiguousarray(np.stack([z, np.ones_like(z), np.zeros_like(z)], 1).astype(np.float32))
+
+
+def reference_forward(cam, means3D, opacities, kw: dict, bg=(0.0, 0.0, 0.0), sh_degree=3) -> dict:
+    """kw: the oracle's colour / covariance keywords (shs or colors_precomp;
+    scales + rotations or cov3D_precomp)."""
+    s = O.settings_from_camera(cam, bg=bg, sh_degree=sh_degree)
+    fwd = O.forward(s, means3D, opacities, **kw)
+    s0 = O.settings_from_camera(cam, bg=(0.0, 0.0, 0.0), sh_degree=sh_degree)
+    kwa = {k: v for k, v in kw.items() if k not in ("shs", "colors_precomp")}
+    kwa["colors_precomp"] = aux_features(fwd.depths)
+    aux = O.forward(s0, means3D, opacities, **kwa)
+    assert np.array_equal(aux.n_contrib, fwd.n_contrib)  # the same contributors
+    return dict(s=s, s0=s0, fwd=fwd, aux=aux, kw=kw, kwa=kwa, cam=cam, means3D=means3D,
+                depth=aux.color[0:1].copy(), alpha=aux.color[1:2].copy())
+
+
+def _aux_cotangent(ref, dL_ddepth, dL_dalpha) -> np.ndarray:
+    H, W = int(ref["s"].image_height), int(ref["s"].image_width)
+    z = np.zeros((1, H, W), np.float32)
+    dd = z if dL_ddepth is None else np.asarray(dL_ddepth, np.float32).reshape(1, H, W)
+    da = z if dL_dalpha is None else np.asarray(dL_dalpha, np.float32).reshape(1, H, W)
+    return np.ascontiguousarray(np.concatenate([dd, da, z], 0))
+
+
+def _zaxis(ref) -> np.ndarray:
+    return np.asarray(ref["cam"].world_view_transform, np.float64)[:3, 2]
+
+
+def _add(total: dict, part: dict, names) -> None:
+    for n in names:
+        if n in part and part[n].size:
+            total[n] = part[n].astype(np.float64) + (total[n] if n in total else 0.0)
+
+
+def reference_backward(ref, dL_dcolor=None, dL_ddepth=None, dL_dalpha=None) -> dict:
+    """The composite reference gradients (float64 sums of the float32 oracle
+    passes); any cotangent may be None."""
+    total: dict = {}
+    if dL_ddepth is not None or dL_dalpha is not None:
+        ga = O.backward(ref["s0"], ref["aux"], ref["means3D"], _aux_cotangent(ref, dL_ddepth, dL_dalpha),
+                        **ref["kwa"])
+        _add(total, ga, SUMMED)
+        total["dL_dmeans3D"] = total["dL_dmeans3D"] + ga["dL_dcolors"][:, 0:1].astype(np.float64) * _zaxis(ref)[None]
+    if dL_dcolor is not None:
+        gc = O.backward(ref["s"], ref["fwd"], ref["means3D"], np.asarray(dL_dcolor, np.float32), **ref["kw"])
+        _add(total, gc, SUMMED + COLOUR_ONLY)
+    else:  # the colour took no part: its own gradients are zero
+        P = ref["fwd"].radii.shape[0]
+        total["dL_dcolors"] = np.zeros((P, 3))
+        if "shs" in ref["kw"]:
+            total["dL_dsh"] = np.zeros(np.asarray(ref["kw"]["shs"]).shape)
+    return total
+
+
+def reference_allowance(ref, dL_dcolor=None, dL_ddepth=None, dL_dalpha=None) -> dict:
+    total: dict = {}
+    if dL_ddepth is not None or dL_dalpha is not None:
+        aa, _ = O.grad_allowance(ref["s0"], ref["aux"], ref["means3D"], _aux_cotangent(ref, dL_ddepth, dL_dalpha),
+                                 **ref["kwa"])
+        _add(total, aa, SUMMED)
+        total["dL_dmeans3D"] = total["dL_dmeans3D"] + aa["dL_dcolors"][:, 0:1] * np.abs(_zaxis(ref))[None]
+    if dL_dcolor is not None:
+        ac, _ = O.grad_allowance(ref["s"], ref["fwd"], ref["means3D"], np.asarray(dL_dcolor, np.float32),
+                                 **ref["kw"])
+        _add(total, ac, SUMMED + COLOUR_ONLY)
+    return total

@@ -1,0 +1,433 @@
+"""The differentiable depth and alpha maps of the base rasterizer on the GPU
+(`_C.rasterize_gaussians_aux` / `_backward_aux`, `rasterize_gaussians_aux`,
+`GaussianRasterizer(..., return_aux=True)`, `renderer.render(...,
+return_aux=True)`, `gs_rasterizer_forward_aux` / `gs_rasterizer_backward_aux`)
+against the composite oracle reference of aux_reference.py.
+
+Bars: the colour image, the radii and the buffers of an aux forward are the
+plain forward's bits; alpha within the project's image bar (L1 < 1e-5), depth
+within that bar scaled by the largest visible depth (the blend is linear in
+the feature); gradients within 1e-4 relative (L2) and the element-wise bar
+with the summed allowances of the reference's two passes.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import aux_reference as AR
+import gs_helpers as G
+from gaussian_splatting_with_eye_tracking_amd import synthetic as S
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+CASES = [
+    ("g1_64_32x32", 64, 32, 32, 3),               # smallest
+    ("ragged_3k_250x130", 3000, 250, 130, 7),     # ragged right and bottom tiles
+    ("dense_20k_128", 20000, 128, 128, 11),       # lists longer than one LDS batch, large-tile sort path
+]
+BG = (0.1, 0.2, 0.3)
+NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
+         "dL_drotations"]
+
+
+def _colors(P, seed):
+    return np.random.default_rng(seed + 5).uniform(0, 1, (P, 3)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(P, W, H, seed, variant):
+    """One oracle reference per (case, variant), shared and left unchanged."""
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    if variant == "sh":
+        kw = dict(shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
+    else:
+        kw = dict(colors_precomp=_colors(P, seed), scales=sc.scales, rotations=sc.rotations)
+    return sc, cam, AR.reference_forward(cam, sc.means3D, sc.opacities, kw, bg=BG)
+
+
+def _cotangents(W, H, seed):
+    dpix = S.make_cotangent(H, W, seed + 1)
+    dd = np.ascontiguousarray(S.make_cotangent(H, W, seed + 2)[0:1])
+    da = np.ascontiguousarray(S.make_cotangent(H, W, seed + 3)[0:1])
+    return dpix, dd, da
+
+
+def _operands(sc, cam, variant, seed, bg=BG):
+    s = G.torch_settings(cam, bg=bg)
+    t = G.scene_tensors(sc)
+    e = torch.Tensor([])
+    sh = t["shs"] if variant == "sh" else e
+    col = e if variant == "sh" else torch.from_numpy(_colors(sc.means3D.shape[0], seed)).cuda()
+    return s, t, sh, col
+
+
+def _forward(C, fn, s, t, sh, col):
+    e = torch.Tensor([])
+    out = fn(s.bg, t["means3D"], col, t["opacities"], t["scales"], t["rotations"], s.scale_modifier, e,
+             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+             s.campos, s.prefiltered, s.debug)
+    torch.cuda.synchronize()
+    return out
+
+
+def _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da):
+    e = torch.Tensor([])
+    W, H = s.image_width, s.image_height
+    cu = lambda a: e.cuda() if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    dp = torch.zeros((3, H, W), device="cuda") if dpix is None else cu(dpix)
+    g = C.rasterize_gaussians_backward_aux(s.bg, t["means3D"], radii, col, t["scales"], t["rotations"],
+                                           s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dp,
+                                           cu(dd), cu(da), sh, s.sh_degree, s.campos, geom, K, binning, img, False)
+    torch.cuda.synchronize()
+    return g
+
+
+def _backward_plain(C, s, t, sh, col, radii, geom, K, binning, img, dpix):
+    e = torch.Tensor([])
+    g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, col, t["scales"], t["rotations"], s.scale_modifier,
+                                       e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
+                                       torch.from_numpy(dpix).cuda(), sh, s.sh_degree, s.campos, geom, K, binning, img,
+                                       False)
+    torch.cuda.synchronize()
+    return g
+
+
+def _assert_same_buffers(C, a, b, P, K, W, H, vis):
+    """Every field of the two forwards' geometry / image / binning buffers
+    (per-Gaussian records of the visible Gaussians: the culled ones' are never
+    written; header: the words a forward defines whatever the binning
+    buffer's capacity)."""
+    da = C.parse_buffers(*a, P, K, W, H, 16)
+    db = C.parse_buffers(*b, P, K, W, H, 16)
+    assert set(da) == set(db)
+    per_gaussian = {"depths", "means2D", "conic_opacity", "rgb", "clamped_bits", "cov3D"}
+    # AMR / scratch words, and the geometry buffer's own radii slot: the
+    # binding hands the forward its radii tensor (compared by the caller), so
+    # the slot is never written
+    skip = {"hdr", "levels", "levels_last", "levels_current", "pv", "tile_count", "radii"}
+    for k in da:
+        if k in skip:
+            continue
+        if k in per_gaussian:
+            if k != "cov3D":  # (written on request only)
+                assert torch.equal(da[k][vis], db[k][vis]), k
+        else:
+            assert torch.equal(da[k], db[k]), k
+    for w in (0, 2, 3, 7):  # K, the tile statistics, the drgb flag
+        assert int(da["hdr"][w]) == int(db["hdr"][w]), w
+    assert (int(da["hdr"][6]) != 0) == (int(db["hdr"][6]) != 0)  # hit codes left (compared above)
+
+
+# --------------------------------------------------------------- 1. forward
+@pytest.mark.parametrize("name,P,W,H,seed", CASES)
+def test_forward_parity(name, P, W, H, seed):
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    sc, cam, ref = _reference(P, W, H, seed, "sh")
+    s, t, sh, col = _operands(sc, cam, "sh", seed)
+    K0, color0, radii0, geom0, bin0, img0 = _forward(C, C.rasterize_gaussians, s, t, sh, col)
+    K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    assert K == K0 == ref["fwd"].num_rendered
+    assert depth.shape == (1, H, W) and alpha.shape == (1, H, W)
+    assert depth.dtype == torch.float32 and alpha.dtype == torch.float32
+    assert torch.equal(color, color0) and torch.equal(radii, radii0)
+    assert geom.numel() == geom0.numel() and img.numel() == img0.numel()
+    _assert_same_buffers(C, (geom, binning, img), (geom0, bin0, img0), P, K, W, H, radii0 > 0)
+    zmax = float(ref["fwd"].depths[ref["fwd"].radii > 0].max())
+    assert zmax < 20.0
+    l1a = G.image_l1(alpha.cpu().numpy(), ref["alpha"])
+    l1d = G.image_l1(depth.cpu().numpy(), ref["depth"])
+    print(f"{name}: alpha L1 {l1a:.3e}, depth L1 {l1d:.3e} (bar {G.IMAGE_L1_TOL * zmax:.3e}, max z {zmax:.3f})")
+    assert l1a < G.IMAGE_L1_TOL
+    assert l1d < G.IMAGE_L1_TOL * zmax
+    # alpha = 1 - final T up to rounding
+    d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
+    assert float((alpha.reshape(-1) - (1.0 - d["accum_alpha"])).abs().max()) < 1e-5
+
+
+# -------------------------------------------------------------- 2. backward
+def _check_against_reference(case, grads, ref, sc, cam, dpix, dd, da):
+    rg = AR.reference_backward(ref, dpix, dd, da)
+    al = AR.reference_allowance(ref, dpix, dd, da)
+    for n, g in zip(NAMES, grads):
+        gg = g.cpu().numpy()
+        assert np.all(np.isfinite(gg)), n
+        if n not in rg:  # (no SH input: an empty gradient)
+            assert n == "dL_dsh" and gg.size == 0, n
+            continue
+        assert gg.shape == rg[n].shape, n
+        err = G.rel_err(gg, rg[n])
+        print(f"{case} {n}: rel err {err:.3e}")
+        assert err < G.GRAD_REL_TOL, (n, err)
+    G.assert_grads_elementwise(case, NAMES, grads, rg, sc, cam, ref["fwd"], allow=al)
+
+
+@pytest.mark.parametrize("name,P,W,H,seed", CASES)
+@pytest.mark.parametrize("variant", ["sh", "colors_precomp"])
+def test_backward_parity(name, P, W, H, seed, variant):
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    sc, cam, ref = _reference(P, W, H, seed, variant)
+    s, t, sh, col = _operands(sc, cam, variant, seed)
+    K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    dpix, dd, da = _cotangents(W, H, seed)
+    grads = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
+    _check_against_reference(f"aux_backward_{name}_{variant}", grads, ref, sc, cam, dpix, dd, da)
+
+
+# ------------------------------------------------- 3. linearity and absence
+@pytest.mark.parametrize("name,P,W,H,seed", CASES)
+@pytest.mark.parametrize("which", ["depth", "alpha"])
+def test_single_aux_cotangent(name, P, W, H, seed, which):
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    sc, cam, ref = _reference(P, W, H, seed, "sh")
+    s, t, sh, col = _operands(sc, cam, "sh", seed)
+    K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    _, dd, da = _cotangents(W, H, seed)
+    dd, da = (dd, None) if which == "depth" else (None, da)
+    grads = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, None, dd, da)
+    _check_against_reference(f"aux_only_{which}_{name}", grads, ref, sc, cam, None, dd, da)
+    if which == "alpha":  # no depth cotangent: no colour and no SH gradient at all
+        assert float(grads[1].abs().max()) == 0.0 and float(grads[5].abs().max()) == 0.0
+
+
+def _function_grads(fn, s, t, loss_of):
+    keys = ("means3D", "opacities", "shs", "scales", "rotations")
+    leaves = {k: t[k].detach().clone().requires_grad_(True) for k in keys}
+    m2 = torch.zeros_like(leaves["means3D"], requires_grad=True)
+    e = torch.Tensor([])
+    out = fn(leaves["means3D"], m2, leaves["shs"], e, leaves["opacities"], leaves["scales"], leaves["rotations"], e, s)
+    g = torch.autograd.grad(loss_of(out), [leaves[k] for k in keys] + [m2])
+    torch.cuda.synchronize()
+    return out, dict(zip(keys + ("means2D",), g))
+
+
+@pytest.mark.parametrize("name,P,W,H,seed", CASES)
+def test_colour_only_through_aux_function_equals_plain(name, P, W, H, seed):
+    from gaussian_splatting_with_eye_tracking_amd.rasterization import rasterize_gaussians, rasterize_gaussians_aux
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    s = G.torch_settings(cam, bg=BG)
+    t = G.scene_tensors(sc)
+    dpix = torch.from_numpy(S.make_cotangent(H, W, seed + 1)).cuda()
+    out0, g0 = _function_grads(rasterize_gaussians, s, t, lambda o: (o[0] * dpix).sum())
+    out1, g1 = _function_grads(rasterize_gaussians_aux, s, t, lambda o: (o[0] * dpix).sum())
+    assert len(out0) == 2 and len(out1) == 4
+    assert torch.equal(out0[0], out1[0]) and torch.equal(out0[1], out1[1])
+    for k in g0:
+        err = G.rel_err(g1[k].cpu().numpy(), g0[k].cpu().numpy())
+        assert err < 1e-5, (k, err)  # (float atomics: run-order noise)
+
+
+# ------------------------------------------------------- 4. autograd drop-in
+def test_autograd_dropin_matches_direct_binding():
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    from diff_gaussian_rasterization import GaussianRasterizer
+    name, P, W, H, seed = CASES[1]
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    s = G.torch_settings(cam, bg=BG)
+    t = G.scene_tensors(sc, requires_grad=True)
+    m2 = torch.zeros_like(t["means3D"], requires_grad=True)
+    ras = GaussianRasterizer(s)
+    kw = dict(means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=t["shs"], scales=t["scales"],
+              rotations=t["rotations"])
+    plain = ras(**kw)
+    assert isinstance(plain, tuple) and len(plain) == 2
+    assert len(ras(return_aux=False, **kw)) == 2
+    color, radii, depth, alpha = ras(return_aux=True, **kw)
+    assert torch.equal(color, plain[0]) and torch.equal(radii, plain[1])
+    assert depth.requires_grad and alpha.requires_grad and not radii.requires_grad
+    dpix, dd, _ = _cotangents(W, H, seed)
+    dpix_t, wd = torch.from_numpy(dpix).cuda(), torch.from_numpy(dd).cuda()
+    loss = (depth / (alpha + 1e-6) * wd).sum() + (color * dpix_t).sum()
+    loss.backward()
+    torch.cuda.synchronize()
+    for k in ("means3D", "opacities", "scales", "rotations", "shs"):
+        assert t[k].grad is not None and torch.isfinite(t[k].grad).all() and float(t[k].grad.abs().max()) > 0, k
+    assert torch.all(m2.grad[:, 2] == 0)
+    # the same cotangents through the direct binding
+    a, d = alpha.detach(), depth.detach()
+    dL_dd = (wd / (a + 1e-6)).cpu().numpy()
+    dL_da = (-wd * d / (a + 1e-6) ** 2).cpu().numpy()
+    td = G.scene_tensors(sc)
+    e = torch.Tensor([])
+    K, c2, d2, a2, r2, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, td, td["shs"], e)
+    assert torch.equal(d2, d) and torch.equal(a2, a) and torch.equal(c2, color.detach())
+    g = _backward_aux(C, s, td, td["shs"], e, r2, geom, K, binning, img, dpix, dL_dd, dL_da)
+    direct = dict(zip(NAMES, g))
+    for k, n in (("means3D", "dL_dmeans3D"), ("opacities", "dL_dopacity"), ("scales", "dL_dscales"),
+                 ("rotations", "dL_drotations"), ("shs", "dL_dsh")):
+        err = G.rel_err(t[k].grad.cpu().numpy(), direct[n].cpu().numpy())
+        assert err < 1e-5, (k, err)
+    assert G.rel_err(m2.grad.cpu().numpy(), direct["dL_dmeans2D"].cpu().numpy()) < 1e-5
+
+
+class _Cam:
+    def __init__(self, cam):
+        self.image_height, self.image_width = int(cam.image_height), int(cam.image_width)
+        self.FoVx, self.FoVy = 2.0 * np.arctan(cam.tanfovx), 2.0 * np.arctan(cam.tanfovy)
+        self.world_view_transform = torch.from_numpy(cam.world_view_transform).cuda()
+        self.full_proj_transform = torch.from_numpy(cam.full_proj_transform).cuda()
+        self.camera_center = torch.from_numpy(cam.camera_center).cuda()
+
+
+class _Model:
+    active_sh_degree = max_sh_degree = 3
+
+    def __init__(self, t):
+        self.get_xyz, self.get_opacity, self.get_features = t["means3D"], t["opacities"], t["shs"]
+        self.get_scaling, self.get_rotation = t["scales"], t["rotations"]
+
+
+class _Pipe:
+    debug = compute_cov3D_python = convert_SHs_python = False
+
+
+def test_renderer_return_aux_keys():
+    from gaussian_splatting_with_eye_tracking_amd.renderer import render
+    name, P, W, H, seed = CASES[0]
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    t = G.scene_tensors(sc, requires_grad=True)
+    bg = torch.tensor(BG, device="cuda")
+    plain = render(_Cam(cam), _Model(t), _Pipe(), bg)
+    assert set(plain) == {"render", "viewspace_points", "visibility_filter", "radii"}
+    out = render(_Cam(cam), _Model(t), _Pipe(), bg, return_aux=True)
+    assert set(out) == set(plain) | {"depth", "alpha"}
+    assert out["depth"].shape == (1, H, W) and out["alpha"].shape == (1, H, W)
+    assert torch.equal(out["render"], plain["render"])
+    (out["depth"].sum() + out["alpha"].sum()).backward()
+    assert t["means3D"].grad is not None and float(t["means3D"].grad.abs().max()) > 0
+    assert out["viewspace_points"].grad is not None
+
+
+# ------------------------------------------------------------- 5. edge cases
+def test_empty_scene():
+    from diff_gaussian_rasterization import GaussianRasterizer
+    sc, cam = G.scene_and_camera(0, 64, 48)
+    s = G.torch_settings(cam)
+    t = G.scene_tensors(sc)
+    color, radii, depth, alpha = GaussianRasterizer(s)(
+        means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], shs=t["shs"],
+        scales=t["scales"], rotations=t["rotations"], return_aux=True)
+    assert color.shape == (3, 48, 64) and torch.all(color == 0) and radii.numel() == 0
+    assert depth.shape == (1, 48, 64) and torch.all(depth == 0)
+    assert alpha.shape == (1, 48, 64) and torch.all(alpha == 0)
+
+
+def test_all_culled():
+    """Every Gaussian behind the near plane: K = 0, zero maps, zero gradients."""
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    sc, cam = G.scene_and_camera(500, 64, 48)
+    sc.means3D[:, 2] = -5.0
+    s, t, sh, col = _operands(sc, cam, "sh", 0, bg=(0.5, 0.25, 0.125))
+    K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    assert K == 0 and torch.all(radii == 0)
+    np.testing.assert_allclose(color.cpu().numpy()[:, 0, 0], [0.5, 0.25, 0.125])
+    assert torch.all(depth == 0) and torch.all(alpha == 0)
+    dpix, dd, da = _cotangents(64, 48, 0)
+    for g in _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da):
+        assert torch.all(g == 0)
+
+
+def test_second_aux_backward_and_plain_backward_after_aux_forward():
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    name, P, W, H, seed = CASES[1]
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    s, t, sh, col = _operands(sc, cam, "sh", seed)
+    dpix, dd, da = _cotangents(W, H, seed)
+    K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    g1 = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
+    g2 = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
+    for n, a, b in zip(NAMES, g1, g2):
+        assert G.rel_err(b.cpu().numpy(), a.cpu().numpy()) < 1e-5, n
+    # a plain backward on the aux forward's buffers (after the aux backwards, and on a fresh aux forward)
+    K0, color0, radii0, geom0, bin0, img0 = _forward(C, C.rasterize_gaussians, s, t, sh, col)
+    ref = _backward_plain(C, s, t, sh, col, radii0, geom0, K0, bin0, img0, dpix)
+    again = _backward_plain(C, s, t, sh, col, radii, geom, K, binning, img, dpix)
+    Kf, _, _, _, radf, geomf, binf, imgf = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    fresh = _backward_plain(C, s, t, sh, col, radf, geomf, Kf, binf, imgf, dpix)
+    for n, r, a, f in zip(NAMES, ref, again, fresh):
+        assert G.rel_err(a.cpu().numpy(), r.cpu().numpy()) < 1e-5, n
+        assert G.rel_err(f.cpu().numpy(), r.cpu().numpy()) < 1e-5, n
+    # ... and an aux backward after a plain backward of one forward
+    g3 = _backward_aux(C, s, t, sh, col, radf, geomf, Kf, binf, imgf, dpix, dd, da)
+    for n, a, b in zip(NAMES, g1, g3):
+        assert G.rel_err(b.cpu().numpy(), a.cpu().numpy()) < 1e-5, n
+
+
+def test_deterministic_mode_refuses_aux_cotangents():
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    from gaussian_splatting_with_eye_tracking_amd import rasterization as R
+    name, P, W, H, seed = CASES[0]
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    s = G.torch_settings(cam, bg=BG)
+    t = G.scene_tensors(sc)
+    try:
+        R.set_deterministic(True)
+        with pytest.raises(RuntimeError, match="deterministic"):
+            _function_grads(R.rasterize_gaussians_aux, s, t, lambda o: o[2].sum() + o[0].sum())
+        # the colour alone still takes the deterministic backward
+        _, g = _function_grads(R.rasterize_gaussians_aux, s, t, lambda o: o[0].sum())
+        assert all(torch.isfinite(v).all() for v in g.values())
+        # the direct binding under the native flag refuses too
+        s2, t2, sh, col = _operands(sc, cam, "sh", seed)
+        K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s2, t2, sh, col)
+        dpix, dd, da = _cotangents(W, H, seed)
+        with pytest.raises(RuntimeError, match="deterministic"):
+            _backward_aux(C, s2, t2, sh, col, radii, geom, K, binning, img, dpix, dd, da)
+    finally:
+        R.set_deterministic(None)
+    assert not C.get_deterministic_backward()
+    _, g = _function_grads(R.rasterize_gaussians_aux, s, t, lambda o: o[2].sum() + o[0].sum())
+    assert all(torch.isfinite(v).all() for v in g.values())
+
+
+# ------------------------------------------------------------------ 6. C ABI
+def test_c_abi_through_ctypes_matches_the_binding():
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    import test_gpu_capi_ctypes as T
+    VP, I, F = T.VP, T.I, T.F
+    lib = T._lib()
+    fwd = [T.GsBuffer] * 3 + [I, I, I, VP, I, I, VP, VP, VP, VP, VP, F, VP, VP, VP, VP, VP, F, F, I]
+    lib.gs_rasterizer_forward_aux.argtypes = fwd + [VP, VP, VP, VP, I, VP]
+    lib.gs_rasterizer_backward_aux.argtypes = ([I, I, I, I, VP, I, I, VP, VP, VP, VP, F, VP, VP, VP, VP, VP, F, F, VP,
+                                                VP, VP, VP, VP, VP, VP] + [VP] * 9 + [I, VP])
+    lib.gs_rasterizer_forward_aux.restype = lib.gs_rasterizer_backward_aux.restype = ctypes.c_int
+    name, P, W, H, seed = CASES[1]
+    sc, cam = G.scene_and_camera(P, W, H, seed)
+    s, t, sh, col = _operands(sc, cam, "sh", seed)
+    dpix, dd, da = _cotangents(W, H, seed)
+    K0, col0, dep0, alp0, rad0, gb0, bb0, ib0 = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    g0 = _backward_aux(C, s, t, sh, col, rad0, gb0, K0, bb0, ib0, dpix, dd, da)
+    dpix_t, dd_t, da_t = (torch.from_numpy(a).cuda() for a in (dpix, dd, da))
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    bufs = T.Buffers(t["means3D"].device)
+    p = T._p
+    with torch.cuda.stream(stream):
+        colr = torch.empty((3, H, W), device="cuda")
+        dep = torch.empty((1, H, W), device="cuda")
+        alp = torch.empty((1, H, W), device="cuda")
+        radii = torch.empty(P, dtype=torch.int32, device="cuda")
+        K = T._check(lib, lib.gs_rasterizer_forward_aux(
+            bufs.buf("geom"), bufs.buf("binning"), bufs.buf("image"), P, 3, 16, p(s.bg), W, H, p(t["means3D"]),
+            p(t["shs"]), VP(0), p(t["opacities"]), p(t["scales"]), F(1.0), p(t["rotations"]), VP(0),
+            p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx), F(s.tanfovy), 0, p(colr), p(radii), p(dep),
+            p(alp), 0, VP(stream.cuda_stream)), "gs_rasterizer_forward_aux")
+        outs = [torch.empty(shape, device="cuda") for shape in ((P, 3), (P, 1), (P, 3), (P, 3), (P, 6), (P, 16, 3),
+                                                                (P, 3), (P, 4))]
+        m2, op, cl, m3, cv, shg, scl, rot = outs
+        T._check(lib, lib.gs_rasterizer_backward_aux(
+            P, 3, 16, K, p(s.bg), W, H, p(t["means3D"]), p(t["shs"]), VP(0), p(t["scales"]), F(1.0),
+            p(t["rotations"]), VP(0), p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx), F(s.tanfovy),
+            p(radii), p(bufs.t["geom"]), p(bufs.t["binning"]), p(bufs.t["image"]), p(dpix_t), p(dd_t), p(da_t), p(m2),
+            VP(0), p(op), p(cl), p(m3), p(cv), p(shg), p(scl), p(rot), 0, VP(stream.cuda_stream)),
+            "gs_rasterizer_backward_aux")
+    stream.synchronize()
+    assert K == K0 > 0
+    assert torch.equal(radii, rad0) and torch.equal(colr, col0)
+    assert torch.equal(dep, dep0) and torch.equal(alp, alp0)
+    mine = dict(zip(NAMES, [m2, cl, op, m3, cv, shg, scl, rot]))
+    for n, ref in zip(NAMES, g0):
+        assert mine[n].shape == ref.shape, n
+        assert G.rel_err(mine[n].cpu().numpy(), ref.cpu().numpy()) < 1e-5, n
