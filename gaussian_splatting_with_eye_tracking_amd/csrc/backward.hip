@@ -868,7 +868,13 @@ void launch_amr_render_backward(int W, int H, int mode, const ImageView& img, co
 // kDrgb: the host knows the forward stored d(rgb)/d(dir) (no SH coefficient
 // path compiled: 114 instead of 164 VGPRs); the SH basis and dL/drgb are
 // returned in sh19 (16 + 3) for the caller's staged dL_dsh stores.
-template <bool kHasSH, bool kHasScales, bool kSH16, bool kDrgb = false>
+// kAA: the backward of an antialiased forward (BackwardGaussArgs::antialiasing):
+// acc[8] is dL/d(conic_opacity.w), conic_opacity.w = opacity * coef, so
+// dL_dopacity = acc[8] * coef and acc[8] * opacity goes back through coef into
+// the 2D covariance (gs_bwd_math.cuh cov2d_backward<true>): one more 4-B load
+// per visible Gaussian.  Either form checks the header word the forward left
+// (kHdrAntialias) against its own flag.
+template <bool kHasSH, bool kHasScales, bool kSH16, bool kDrgb = false, bool kAA = false>
 __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& a,
                                                        const float* __restrict__ grad_accum,
                                                        const uint8_t* __restrict__ clamped_bits, int idx,
@@ -887,6 +893,15 @@ __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& 
     } else {
 #pragma unroll
         for (int q = 0; q < kNG; q++) acc[q] = 0.f;
+    }
+    // a forward of the other mode wrote these buffers: raise through the header's
+    // error word and poison the gradients rather than return wrong ones (uniform)
+    if (a.err_word && (a.hdr[kHdrAntialias] != 0u) != kAA) {
+        if (idx == 0) *a.err_word = a.err_token;
+        if (vis) {
+#pragma unroll
+            for (int q = 0; q < kNG; q++) acc[q] = __uint_as_float(0x7fc00000u);
+        }
     }
     // (dL_dcolor, dL_dconic, dL_dcov3D: NULL = not wanted -- the autograd
     // wrapper discards them unless the matching precomputed input was given;
@@ -909,10 +924,12 @@ __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& 
         a.dL_dmean2D[3 * idx + 2] = 0.f;
     }
     if (a.dL_dconic) reinterpret_cast<float4*>(a.dL_dconic)[idx] = make_float4(acc[5], acc[6], 0.f, acc[7]);
-    store_out1(&a.dL_dopacity[idx], acc[8], a.nt_out != 0);
+    // (kAA: acc[8] * coef, once cov2d_backward has the coefficient)
+    if constexpr (!kAA) store_out1(&a.dL_dopacity[idx], acc[8], a.nt_out != 0);
 
     const int ncoef_out = a.M;  // dL_dsh is [P, M, 3]
     if (!vis) {
+        if constexpr (kAA) store_out1(&a.dL_dopacity[idx], 0.f, a.nt_out != 0);
         if (small) {
 #pragma unroll
             for (int i = 3; i < 9; i++) (*small)[i] = 0.f;
@@ -962,6 +979,8 @@ __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& 
 #pragma unroll
         for (int i = 0; i < 6; i++) cov3D[i] = a.cov3D[6 * idx + i];
     }
+    float opac = 0.f;  // (kAA) the forward's input opacity
+    if constexpr (kAA) opac = a.opacities[idx];
     float s[16][3];
     uint8_t cb = 0;
     // the forward's d(rgb)/d(dir) when it stored them: no SH coefficients read
@@ -1003,8 +1022,15 @@ __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& 
     // ---- computeCov2DCUDA (backward.cu:144-274)
     float dmean[3];
     float dcov[6];
-    cov2d_backward(mx, my, mz, cov3D, acc[5], acc[6], acc[7], V, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy,
-                   dmean, dcov);
+    if constexpr (kAA) {
+        float coef;
+        cov2d_backward<true>(mx, my, mz, cov3D, acc[5], acc[6], acc[7], V, a.focal_x, a.focal_y, a.tan_fovx,
+                             a.tan_fovy, dmean, dcov, acc[8] * opac, &coef);
+        store_out1(&a.dL_dopacity[idx], acc[8] * coef, a.nt_out != 0);
+    } else {
+        cov2d_backward(mx, my, mz, cov3D, acc[5], acc[6], acc[7], V, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy,
+                       dmean, dcov);
+    }
     if (a.dL_dcov3D) {
 #pragma unroll
         for (int i = 0; i < 6; i++) a.dL_dcov3D[6 * idx + i] = dcov[i];
@@ -1061,7 +1087,7 @@ __device__ __forceinline__ void backward_gaussian_body(const BackwardGaussArgs& 
 constexpr int kBgStageNt = 16;  // backward_gaussians_kernel stage flag: dL_dsh rows non-temporal
 
 
-template <bool kHasSH, bool kHasScales, bool kSH16, bool kSmall = false>
+template <bool kHasSH, bool kHasScales, bool kSH16, bool kSmall = false, bool kAA = false>
 __global__ void __launch_bounds__(256) backward_gaussians_kernel(BackwardGaussArgs a, const float* __restrict__ grad_accum,
                                                                  const uint8_t* __restrict__ clamped_bits, int stage) {
     constexpr bool kStage = kHasSH && kSH16;
@@ -1101,9 +1127,9 @@ __global__ void __launch_bounds__(256) backward_gaussians_kernel(BackwardGaussAr
     // 32-B granule per lane per instruction: ~+23 % write bytes at config 4,
     // profiles/r04d_cfg4_pmc_summary.json)
     float small[12];
-    backward_gaussian_body<kHasSH, kHasScales, kSH16>(a, grad_accum, clamped_bits, idx,
-                                                      kStage ? s_dsh + threadIdx.x * kShRow : nullptr,
-                                                      kSmall ? &small : nullptr);
+    backward_gaussian_body<kHasSH, kHasScales, kSH16, false, kAA>(a, grad_accum, clamped_bits, idx,
+                                                                  kStage ? s_dsh + threadIdx.x * kShRow : nullptr,
+                                                                  kSmall ? &small : nullptr);
     if constexpr (kStage) {
         __syncthreads();
         const int g0 = blockIdx.x * blockDim.x;
@@ -1143,6 +1169,7 @@ __global__ void __launch_bounds__(256) backward_gaussians_kernel(BackwardGaussAr
 // 192-B dL_dsh rows staged through a half-size LDS area in two rounds of 128
 // Gaussians (25 KB, recomputed from the 16 basis values and dL/drgb each
 // thread keeps), then the small outputs as in backward_gaussians_kernel.
+template <bool kAA = false>
 __global__ void __launch_bounds__(256) backward_gaussians_drgb_kernel(BackwardGaussArgs a,
                                                                       const float* __restrict__ grad_accum,
                                                                       const uint8_t* __restrict__ clamped_bits,
@@ -1150,7 +1177,7 @@ __global__ void __launch_bounds__(256) backward_gaussians_drgb_kernel(BackwardGa
     __shared__ float s_half[128 * kShRow];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     float small[12], sh19[19];
-    backward_gaussian_body<true, true, true, true>(a, grad_accum, clamped_bits, idx, nullptr, &small, &sh19);
+    backward_gaussian_body<true, true, true, true, kAA>(a, grad_accum, clamped_bits, idx, nullptr, &small, &sh19);
     const int g0 = blockIdx.x * blockDim.x;
     const int n = min(256, a.P - g0);
     const int ncoef = min((a.D + 1) * (a.D + 1), a.M);
@@ -1215,14 +1242,32 @@ void launch_backward_gaussians(const BackwardGaussArgs& args, const GeomView& g,
     const bool sh16 = sh && a.M == 16;
     const bool sc = a.scales != nullptr;
     a.nt_out = 0;
-#define GS_BG_LAUNCH(A, B, C) \
-    hipLaunchKernelGGL((backward_gaussians_kernel<A, B, C>), grid, dim3(256), 0, s, a, g.grad_accum, g.clamped, 0)
-    if (sh16 && sc && a.drgb && a.drgb_known && a.P < 4000000)
-        hipLaunchKernelGGL(backward_gaussians_drgb_kernel, grid, dim3(256), 0, s, a, g.grad_accum, g.clamped, 1);
-    else if (sh16 && sc)
-        hipLaunchKernelGGL((backward_gaussians_kernel<true, true, true, true>), grid, dim3(256), 0, s, a,
-                           g.grad_accum, g.clamped, kBgStageNt);
-    else if (sh16) GS_BG_LAUNCH(true, false, true);
+    // (each form twice: the antialiased one reads a.opacities)
+    const bool aa = a.antialiasing != 0;
+#define GS_BG_LAUNCH(A, B, C)                                                                                      \
+    do {                                                                                                           \
+        if (aa)                                                                                                    \
+            hipLaunchKernelGGL((backward_gaussians_kernel<A, B, C, false, true>), grid, dim3(256), 0, s, a,        \
+                               g.grad_accum, g.clamped, 0);                                                        \
+        else                                                                                                       \
+            hipLaunchKernelGGL((backward_gaussians_kernel<A, B, C>), grid, dim3(256), 0, s, a, g.grad_accum,       \
+                               g.clamped, 0);                                                                      \
+    } while (0)
+    if (sh16 && sc && a.drgb && a.drgb_known && a.P < 4000000) {
+        if (aa)
+            hipLaunchKernelGGL(backward_gaussians_drgb_kernel<true>, grid, dim3(256), 0, s, a, g.grad_accum,
+                               g.clamped, 1);
+        else
+            hipLaunchKernelGGL(backward_gaussians_drgb_kernel<false>, grid, dim3(256), 0, s, a, g.grad_accum,
+                               g.clamped, 1);
+    } else if (sh16 && sc) {
+        if (aa)
+            hipLaunchKernelGGL((backward_gaussians_kernel<true, true, true, true, true>), grid, dim3(256), 0, s, a,
+                               g.grad_accum, g.clamped, kBgStageNt);
+        else
+            hipLaunchKernelGGL((backward_gaussians_kernel<true, true, true, true>), grid, dim3(256), 0, s, a,
+                               g.grad_accum, g.clamped, kBgStageNt);
+    } else if (sh16) GS_BG_LAUNCH(true, false, true);
     else if (sh && sc) GS_BG_LAUNCH(true, true, false);
     else if (sh) GS_BG_LAUNCH(true, false, false);
     else if (sc) GS_BG_LAUNCH(false, true, false);

@@ -386,6 +386,8 @@ struct ForwardIn {
     bool store_cov3d;
     bool fwd_zero;        // fwd_zero, and not under the forward-only hint
     bool step0_unfilled;  // AMR forwards only
+    // the Mip-Splatting 2D filter (gs_rasterizer_forward_ex; base forwards only)
+    int antialiasing = 0;
 };
 
 // Per-call token for the header's error word (never 0: a zeroed header at
@@ -464,6 +466,7 @@ PreprocessArgs make_pp(const ForwardIn& in, int tile) {
     a.zero_words = nullptr;
     a.zero_n = 0;
     a.err_token = 0;
+    a.antialiasing = in.antialiasing;
     return a;
 }
 
@@ -631,6 +634,50 @@ const char* gs_build_digest(void) { return GSAMD_DIGEST; }
 
 const char* gs_last_error(void) { return g_err.c_str(); }
 
+namespace {
+// The base forward: preprocess + binning + blend, and with `aux` one replay of
+// the tile lists for the depth and alpha maps.  The plain and the aux entry
+// make the same launches in the same order up to the replay, so the image, the
+// radii and the three buffers are the same bits either way.
+int base_forward_impl(const ForwardIn& in, const gs_buffer& geometry, const gs_buffer& binning,
+                      const gs_buffer& image, float* out_color, int* radii, bool aux, float* out_depth,
+                      float* out_alpha, int debug, void* stream, const char* who) {
+    const int P = in.P, width = in.width, height = in.height;
+    if (aux && (!out_depth || !out_alpha)) throw GsError(std::string(who) + ": out_depth / out_alpha is NULL");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (P <= 0) {
+        if (aux) {  // nothing blended: zero maps
+            const size_t N = (width > 0 && height > 0) ? (size_t)width * (size_t)height : 0;
+            if (N) {
+                GS_HIP(hipMemsetAsync(out_depth, 0, sizeof(float) * N, s));
+                GS_HIP(hipMemsetAsync(out_alpha, 0, sizeof(float) * N, s));
+            }
+        }
+        return 0;
+    }
+    Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
+    const float* feats = in.colors_precomp ? in.colors_precomp : r.g.rgb;
+    bool zeroed;
+    {
+        StageTimer _t(kRender, s, true);
+        // the accumulator rows are zeroed behind the blend only when a
+        // backward can follow (not under the forward-only hint: a later
+        // backward of this forward then zeroes them itself)
+        const bool zero = in.fwd_zero;
+        zeroed = launch_render_forward(width, height, r.img, r.b, r.g, feats, in.background, out_color, s,
+                                       zero ? r.g.grad_accum : nullptr, zero ? (size_t)kGradRow * (size_t)P : 0,
+                                       reinterpret_cast<uint8_t*>(r.b.scratch));
+    }
+    if (zeroed) set_accum_clean(r.g.grad_accum, true);
+    stage_check(debug != 0, s, "render");
+    if (aux) {
+        launch_render_forward_aux(width, height, r.img, r.b, r.g, out_depth, out_alpha, s);
+        stage_check(debug != 0, s, "render_aux");
+    }
+    return r.K;
+}
+}  // namespace
+
 int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
                           const float* background, int width, int height, const float* means3D, const float* shs,
                           const float* colors_precomp, const float* opacities, const float* scales,
@@ -641,30 +688,13 @@ int gs_rasterizer_forward(gs_buffer geometry, gs_buffer binning, gs_buffer image
                                     scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
                                     tan_fovx, tan_fovy, prefiltered);
     return guarded([&]() -> int {
-        if (P <= 0) return 0;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
-        const float* feats = colors_precomp ? colors_precomp : r.g.rgb;
-        bool zeroed;
-        {
-            StageTimer _t(kRender, s, true);
-            // the accumulator rows are zeroed behind the blend only when a
-            // backward can follow (not under the forward-only hint: a later
-            // backward of this forward then zeroes them itself)
-            const bool zero = in.fwd_zero;
-            zeroed = launch_render_forward(width, height, r.img, r.b, r.g, feats, background, out_color, s,
-                                           zero ? r.g.grad_accum : nullptr, zero ? (size_t)kGradRow * (size_t)P : 0,
-                                           reinterpret_cast<uint8_t*>(r.b.scratch));
-        }
-        if (zeroed) set_accum_clean(r.g.grad_accum, true);
-        stage_check(debug != 0, s, "render");
-        return r.K;
+        return base_forward_impl(in, geometry, binning, image, out_color, radii, false, nullptr, nullptr, debug,
+                                 stream, "gs_rasterizer_forward");
     });
 }
 
-// The same forward -- the same launches in the same order, so the image, the
-// radii and the three buffers are the plain call's bits -- followed by one
-// replay of the tile lists for the depth and alpha maps.
+// The same forward followed by one replay of the tile lists for the depth and
+// alpha maps (base_forward_impl).
 int gs_rasterizer_forward_aux(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
                               const float* background, int width, int height, const float* means3D, const float* shs,
                               const float* colors_precomp, const float* opacities, const float* scales,
@@ -676,31 +706,28 @@ int gs_rasterizer_forward_aux(gs_buffer geometry, gs_buffer binning, gs_buffer i
                                     scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
                                     tan_fovx, tan_fovy, prefiltered);
     return guarded([&]() -> int {
-        if (!out_depth || !out_alpha) throw GsError("gs_rasterizer_forward_aux: out_depth / out_alpha is NULL");
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        if (P <= 0) {  // nothing blended: zero maps
-            const size_t N = (width > 0 && height > 0) ? (size_t)width * (size_t)height : 0;
-            if (N) {
-                GS_HIP(hipMemsetAsync(out_depth, 0, sizeof(float) * N, s));
-                GS_HIP(hipMemsetAsync(out_alpha, 0, sizeof(float) * N, s));
-            }
-            return 0;
-        }
-        Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
-        const float* feats = colors_precomp ? colors_precomp : r.g.rgb;
-        bool zeroed;
-        {
-            StageTimer _t(kRender, s, true);
-            const bool zero = in.fwd_zero;
-            zeroed = launch_render_forward(width, height, r.img, r.b, r.g, feats, background, out_color, s,
-                                           zero ? r.g.grad_accum : nullptr, zero ? (size_t)kGradRow * (size_t)P : 0,
-                                           reinterpret_cast<uint8_t*>(r.b.scratch));
-        }
-        if (zeroed) set_accum_clean(r.g.grad_accum, true);
-        stage_check(debug != 0, s, "render");
-        launch_render_forward_aux(width, height, r.img, r.b, r.g, out_depth, out_alpha, s);
-        stage_check(debug != 0, s, "render_aux");
-        return r.K;
+        return base_forward_impl(in, geometry, binning, image, out_color, radii, true, out_depth, out_alpha, debug,
+                                 stream, "gs_rasterizer_forward_aux");
+    });
+}
+
+// The superset forward: the antialiasing flag, and the maps when both are given.
+int gs_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                             const float* background, int width, int height, const float* means3D, const float* shs,
+                             const float* colors_precomp, const float* opacities, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                             float tan_fovy, int prefiltered, int antialiasing, float* out_color, int* radii,
+                             float* out_depth, float* out_alpha, int debug, void* stream) {
+    ForwardIn in = forward_in(false, P, D, M, background, width, height, means3D, shs, colors_precomp, opacities,
+                              scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                              tan_fovx, tan_fovy, prefiltered);
+    in.antialiasing = antialiasing != 0;
+    return guarded([&]() -> int {
+        if ((out_depth == nullptr) != (out_alpha == nullptr))
+            throw GsError("gs_rasterizer_forward_ex: out_depth and out_alpha go together (both, or both NULL)");
+        return base_forward_impl(in, geometry, binning, image, out_color, radii, out_depth != nullptr, out_depth,
+                                 out_alpha, debug, stream, "gs_rasterizer_forward_ex");
     });
 }
 
@@ -785,6 +812,8 @@ void blend_backward(const DetScratch& det, int width, int height, int P, int R, 
 int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
     check_det_scratch(c.det, c.R, "gs_rasterizer_backward_deterministic");
     BackwardGaussArgs a = c.a;
+    if (a.antialiasing && !a.opacities && a.P > 0)
+        throw GsError("gs_rasterizer_backward_ex: the antialiased backward needs the forward's opacities");
     if (a.P <= 0) return 0;
     hipStream_t s = c.s;
     const Binned v = carve_buffers(c.geom_buffer, c.binning_buffer, c.img_buffer, a.P, c.R, c.width, c.height,
@@ -820,8 +849,23 @@ int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
     a.drgb = g.drgb;  // read only where the header says this forward wrote the rows
     a.drgb_known = a.drgb != nullptr && drgb_written(g.drgb);
     a.hdr = g.hdr;
+    // the forward's mode (header word kHdrAntialias) against this call's flag:
+    // a mismatch stores the token in the header's error word and NaNs in the
+    // gradients; a debug call reads the word back and raises
+    a.err_word = g.hdr + kHdrError;
+    a.err_token = next_error_token();
     { StageTimer _t(kBwdGauss, s); launch_backward_gaussians(a, g, s); }
     stage_check(c.debug != 0, s, "preprocess_backward");
+    if (c.debug) {
+        uint32_t err = 0;
+        GS_HIP(hipMemcpy(&err, g.hdr + kHdrError, sizeof(err), hipMemcpyDeviceToHost));
+        if (err == a.err_token)
+            throw GsError(a.antialiasing
+                              ? "backward: antialiasing is set but the forward that wrote these buffers was not "
+                                "antialiased"
+                              : "backward: the forward that wrote these buffers was antialiased; pass antialiasing "
+                                "and its opacities (gs_rasterizer_backward_ex)");
+    }
     if (c.aux && c.dL_ddepth && c.R > 0) {  // the depth map's direct term on the means
         launch_aux_depth_to_means(a.P, g, a.radii, a.viewmatrix, a.dL_dmean3D, s);
         stage_check(c.debug != 0, s, "aux_depth_to_means");
@@ -983,6 +1027,40 @@ int gs_amr_rasterizer_backward(int P, int D, int M, int R, const float* backgrou
             c.dL_dpix = dL_dpix_scratch;
         }
         return rasterizer_backward_impl(foveaStep, c);
+    });
+}
+
+// The superset backward: the antialiasing flag with the forward's opacities,
+// the maps' cotangents, the deterministic blend.
+int gs_rasterizer_backward_ex(int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp,
+                              const float* opacities, const float* scales, float scale_modifier,
+                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                              const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D,
+                              float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                              float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
+                              int deterministic, char* scratch, size_t scratch_bytes, int debug, void* stream) {
+    return guarded([&]() -> int {
+        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
+                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                                       dL_dscale, dL_drot, debug, stream);
+        c.a.opacities = opacities;
+        c.a.antialiasing = antialiasing != 0;
+        if (dL_ddepth || dL_dalpha) {
+            if (deterministic)
+                throw GsError("gs_rasterizer_backward_ex: the deterministic backward takes no depth / alpha cotangents");
+            c.aux = true;
+            c.dL_ddepth = dL_ddepth;
+            c.dL_dalpha = dL_dalpha;
+        } else if (!dL_dpix && P > 0) {
+            throw GsError("gs_rasterizer_backward_ex: every cotangent is NULL");
+        }
+        if (deterministic) c.det = DetScratch{true, scratch, scratch_bytes};
+        return rasterizer_backward_impl(0, c);
     });
 }
 

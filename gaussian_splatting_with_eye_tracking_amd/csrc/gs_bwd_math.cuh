@@ -138,9 +138,20 @@ __device__ __forceinline__ void sh_backward(const BackwardGaussArgs& a, int idx,
 
 // computeCov2DCUDA backward (backward.cu:144-274) for one Gaussian and one
 // view: dL_dconic (x, y, w) -> dmean (assigned, `=`) and dL_dcov3D.
+// kAA (the forward was antialiased, preprocess.hip pp_gaussian kAA): also the
+// coefficient coef = sqrt(max(0.000025, ratio)), ratio = det0 / det1 of the 2D
+// covariance before / after the dilation h = 0.3, returned in *coef, and the
+// pull-back of its cotangent dL_dcoef (= dL/d(conic_opacity.w) * opacity)
+// onto the covariance (a0, b, c0), added to dL_da / dL_db / dL_dc before they
+// go on to dL_dcov3D and the mean:
+//   d ratio / d a0 = h (c0 c + b^2) / det1^2,  d ratio / d c0 = h (a0 a + b^2) / det1^2,
+//   d ratio / d b  = -2 b h (a0 + c0 + h) / det1^2
+// (closed forms without cancellation: c0 det1 - det0 c = h (c0 c + b^2)).
+template <bool kAA = false>
 __device__ __forceinline__ void cov2d_backward(float mx, float my, float mz, const float (&cov3D)[6],
                                                float dcx, float dcy, float dcz, const Mat4& V, float h_x, float h_y,
-                                               float tan_fovx, float tan_fovy, float (&dmean)[3], float (&dcov)[6]) {
+                                               float tan_fovx, float tan_fovy, float (&dmean)[3], float (&dcov)[6],
+                                               float dL_dcoef = 0.f, float* coef = nullptr) {
     float3 t = transform_point_4x3(mx, my, mz, V);
     const float limx = 1.3f * tan_fovx;
     const float limy = 1.3f * tan_fovy;
@@ -158,6 +169,7 @@ __device__ __forceinline__ void cov2d_backward(float mx, float my, float mz, con
                                cov3D[5]);
     const Mat3 T = mat3_mul(Wm, J);
     Mat3 cov2D = mat3_mul(mat3_mul(mat3_transpose(T), mat3_transpose(Vrk)), T);
+    const float a0 = cov2D.m[0][0], c0 = cov2D.m[1][1];  // (kAA: before the dilation)
     const float aa = cov2D.m[0][0] += 0.3f;
     const float bb = cov2D.m[0][1];
     const float cc = cov2D.m[1][1] += 0.3f;
@@ -169,9 +181,20 @@ __device__ __forceinline__ void cov2d_backward(float mx, float my, float mz, con
     // expressions -- the same values; as a branch, the compiler sank the two
     // paths' dcov stores into a pointer phi and kept dcov in scratch memory)
     const bool ok = denom2inv != 0;
-    const float dL_da = ok ? denom2inv * (-cc * cc * dcx + 2 * bb * cc * dcy + (denom - aa * cc) * dcz) : 0.f;
-    const float dL_dc = ok ? denom2inv * (-aa * aa * dcz + 2 * aa * bb * dcy + (denom - aa * cc) * dcx) : 0.f;
-    const float dL_db = ok ? denom2inv * 2 * (bb * cc * dcx - (denom + 2 * bb * bb) * dcy + aa * bb * dcz) : 0.f;
+    float dL_da = ok ? denom2inv * (-cc * cc * dcx + 2 * bb * cc * dcy + (denom - aa * cc) * dcz) : 0.f;
+    float dL_dc = ok ? denom2inv * (-aa * aa * dcz + 2 * aa * bb * dcy + (denom - aa * cc) * dcx) : 0.f;
+    float dL_db = ok ? denom2inv * 2 * (bb * cc * dcx - (denom + 2 * bb * bb) * dcy + aa * bb * dcz) : 0.f;
+    if constexpr (kAA) {
+        const float h = 0.3f;
+        const float ratio = (a0 * c0 - bb * bb) / denom;
+        const float cf = sqrtf(fmaxf(0.000025f, ratio));
+        *coef = cf;
+        const float dL_dratio = ratio <= 0.000025f ? 0.f : dL_dcoef / (2 * cf);
+        const float d1sq = denom * denom;
+        dL_da += ok ? dL_dratio * h * (c0 * cc + bb * bb) / d1sq : 0.f;
+        dL_dc += ok ? dL_dratio * h * (a0 * aa + bb * bb) / d1sq : 0.f;
+        dL_db += ok ? dL_dratio * (-2 * bb * h * (a0 + c0 + h)) / d1sq : 0.f;
+    }
     dcov[0] = ok ? (Tm[0][0] * Tm[0][0] * dL_da + Tm[0][0] * Tm[1][0] * dL_db + Tm[1][0] * Tm[1][0] * dL_dc) : 0.f;
     dcov[3] = ok ? (Tm[0][1] * Tm[0][1] * dL_da + Tm[0][1] * Tm[1][1] * dL_db + Tm[1][1] * Tm[1][1] * dL_dc) : 0.f;
     dcov[5] = ok ? (Tm[0][2] * Tm[0][2] * dL_da + Tm[0][2] * Tm[1][2] * dL_db + Tm[1][2] * Tm[1][2] * dL_dc) : 0.f;

@@ -45,6 +45,9 @@ struct PreprocessArgs {
     uint32_t* zero_words;
     int zero_n;
     uint32_t err_token;
+    // the Mip-Splatting 2D filter: the recorded opacity is the input's times
+    // sqrt(max(0.000025, det cov2D / det (cov2D + 0.3 I))) (base tiles only)
+    int antialiasing = 0;
 };
 
 // base/cr/forward.cu:155-256 (+ the tile histogram the binning needs).
@@ -159,6 +162,15 @@ struct BackwardGaussArgs {
     const uint32_t* hdr;    // the geometry header (kHdrDrgb says whether drgb was written)
     int drgb_known;         // the host knows this geometry buffer's forward wrote drgb (gs_api registry)
     int nt_out = 0;         // the outputs other than dL_dsh stored with the non-temporal hint (off: +3 %)
+    // the forward was antialiased (PreprocessArgs::antialiasing): opacities are
+    // the forward's inputs [P], and the coefficient's gradient joins dL_dopacity
+    // and the 2D covariance's.  A flag that disagrees with the header word
+    // kHdrAntialias stores err_token in err_word (the header's kHdrError) and
+    // NaNs in every gradient of the visible Gaussians.
+    const float* opacities = nullptr;
+    int antialiasing = 0;
+    uint32_t* err_word = nullptr;
+    uint32_t err_token = 0;
     // outputs (every element written; no memsets needed)
     float* dL_dmean2D;
     float* dL_dconic;

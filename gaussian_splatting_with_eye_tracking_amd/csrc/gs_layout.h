@@ -47,6 +47,8 @@ enum HdrWord : int {
     kHdrT = 5,
     kHdrHitCodes = 6,     // != 0: where the base forward render stored exact row-group hit codes (hit_codes_of)
     kHdrDrgb = 7,         // 1: the preprocess stored d(rgb)/d(view dir) of every visible Gaussian (GeomView::drgb)
+    kHdrAntialias = 8,    // 1: the preprocess scaled the opacities by the antialiasing coefficient (0: it did not);
+                          // written by every forward, checked by the per-Gaussian backward
     kHdrWords = 64,
 };
 

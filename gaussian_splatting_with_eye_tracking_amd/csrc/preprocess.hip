@@ -113,7 +113,11 @@ constexpr int kShStride = 52;
 // Everything after the loads of one Gaussian (forward.cu:155-256): the cull,
 // cov2D, conic, radius / rect, SH colour (coefficients from load_shc, only for
 // survivors), the records.  radii / tiles_touched were zeroed by the caller.
-template <bool kHasSH, bool kCovPrecomp, typename ShFn>
+// kAA (PreprocessArgs::antialiasing, base tiles only): the opacity recorded is
+// the input's times sqrt(max(0.000025, det cov / det (cov + 0.3 I))), the
+// Mip-Splatting 2D filter's energy-conserving factor; the
+// conic, radius, rect and depth -- hence the binning -- do not depend on it.
+template <bool kHasSH, bool kCovPrecomp, bool kAA, typename ShFn>
 __device__ __forceinline__ void pp_gaussian(const PreprocessArgs& a, const GeomView& g, int* __restrict__ radii,
                                             uint32_t* __restrict__ tile_count, int idx, bool radii_copy, float mx,
                                             float my, float mz, const float (&sc)[3], float4 q, float (&cov3D)[6],
@@ -158,6 +162,8 @@ __device__ __forceinline__ void pp_gaussian(const PreprocessArgs& a, const GeomV
     const Mat3 Vrk = mat3_cols(cov3D[0], cov3D[1], cov3D[2], cov3D[1], cov3D[3], cov3D[4], cov3D[2], cov3D[4],
                                cov3D[5]);
     Mat3 cov = mat3_mul(mat3_mul(mat3_transpose(T), mat3_transpose(Vrk)), T);
+    float det0 = 0.f;  // the determinant before the dilation
+    if constexpr (kAA) det0 = cov.m[0][0] * cov.m[1][1] - cov.m[0][1] * cov.m[0][1];
     cov.m[0][0] += 0.3f;
     cov.m[1][1] += 0.3f;
     const float cx = cov.m[0][0], cy = cov.m[0][1], cz = cov.m[1][1];
@@ -165,6 +171,7 @@ __device__ __forceinline__ void pp_gaussian(const PreprocessArgs& a, const GeomV
     // EWA inverse + extent (forward.cu:219-237)
     const float det = (cx * cz - cy * cy);
     if (det == 0.0f) return;
+    if constexpr (kAA) opacity = opacity * sqrtf(fmaxf(0.000025f, det0 / det));
     const float det_inv = 1.f / det;
     const float conic_x = cz * det_inv, conic_y = -cy * det_inv, conic_z = cx * det_inv;
     const float mid = 0.5f * (cx + cz);
@@ -248,7 +255,7 @@ __device__ __forceinline__ void pp_gaussian(const PreprocessArgs& a, const GeomV
 
 // One Gaussian: zero its counters, issue its loads, pp_gaussian.  stage: the
 // thread's LDS row for the strided records (kStageOut) or nullptr.
-template <bool kHasSH, bool kSH16, bool kCovPrecomp, bool kDma, bool kNtIn = false>
+template <bool kHasSH, bool kSH16, bool kCovPrecomp, bool kDma, bool kNtIn = false, bool kAA = false>
 __device__ __forceinline__ void pp_thread(const PreprocessArgs& a, const GeomView& g, int* __restrict__ radii,
                                           uint32_t* __restrict__ tile_count, int idx, const float* sh_row,
                                           float* stage) {
@@ -281,7 +288,7 @@ __device__ __forceinline__ void pp_thread(const PreprocessArgs& a, const GeomVie
     const float opacity = ldg1<kNtIn>(a.opacities + idx);
     const Mat4 V = load_mat4(a.viewmatrix);
     const Mat4 Pm = load_mat4(a.projmatrix);
-    pp_gaussian<kHasSH, kCovPrecomp>(a, g, radii, tile_count, idx, radii_copy, mx, my, mz, sc, q, cov3D, opacity,
+    pp_gaussian<kHasSH, kCovPrecomp, kAA>(a, g, radii, tile_count, idx, radii_copy, mx, my, mz, sc, q, cov3D, opacity,
                                      V, Pm, [&](float (&shc)[16][3]) {
         if constexpr (kDma) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA rows have landed
@@ -323,7 +330,7 @@ __device__ __forceinline__ void pp_thread(const PreprocessArgs& a, const GeomVie
 // r04z7_ab_pp*.log).  Measured and removed: per-thread SH loads with LDS-DMA
 // but unstaged records, a persistent pipelined form (0.537 vs 0.502 ms at
 // config 4, profiles/r04e_ab_pp*.log).
-template <bool kHasSH, bool kSH16, bool kCovPrecomp, bool kDma = false>
+template <bool kHasSH, bool kSH16, bool kCovPrecomp, bool kDma = false, bool kAA = false>
 __global__ void __launch_bounds__(kPpThreads) preprocess_kernel(PreprocessArgs a, GeomView g, int* __restrict__ radii,
                                                                 uint32_t* __restrict__ tile_count) {
     static_assert(!kDma || (kHasSH && kSH16), "LDS-DMA stages 16-coefficient SH rows");
@@ -349,12 +356,15 @@ __global__ void __launch_bounds__(kPpThreads) preprocess_kernel(PreprocessArgs a
     // whether the backward may take d(rgb)/d(dir) from g.drgb (every visible
     // Gaussian's row is written below)
     if (idx == 0) g.hdr[kHdrDrgb] = (kHasSH && a.store_drgb) ? 1u : 0u;
+    // whether the recorded opacities carry the antialiasing coefficient (the
+    // per-Gaussian backward refuses a call whose flag says otherwise)
+    if (idx == 0) g.hdr[kHdrAntialias] = kAA ? 1u : 0u;
     float* row = s_sh + (kDma ? kShStride * threadIdx.x : 0);
     if constexpr (kStageOut) {
         // every lane of a wave takes part in its coalesced record stores below
         const int wrow0 = (int)(blockIdx.x * kPpThreads) + (int)(threadIdx.x & ~63u);
         if (wrow0 >= a.P) return;  // wave-uniform
-        if (idx < a.P) pp_thread<kHasSH, kSH16, kCovPrecomp, kDma, kNtIn>(a, g, radii, tile_count, idx, row, row);
+        if (idx < a.P) pp_thread<kHasSH, kSH16, kCovPrecomp, kDma, kNtIn, kAA>(a, g, radii, tile_count, idx, row, row);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -404,14 +414,19 @@ __global__ void __launch_bounds__(kPpThreads) preprocess_kernel(PreprocessArgs a
         return;
     }
     if (idx >= a.P) return;
-    pp_thread<kHasSH, kSH16, kCovPrecomp, kDma>(a, g, radii, tile_count, idx, row, nullptr);
+    pp_thread<kHasSH, kSH16, kCovPrecomp, kDma, false, kAA>(a, g, radii, tile_count, idx, row, nullptr);
 }
 
 template <bool A, bool B, bool C>
 static void launch_pp(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count, hipStream_t s) {
     const int blocks = (a.P + kPpThreads - 1) / kPpThreads;
-    hipLaunchKernelGGL((preprocess_kernel<A, B, C, A && B>), dim3(blocks), dim3(kPpThreads), 0, s, a, g, radii,
-                       tile_count);
+    // (the AMR preprocess, 32-px tiles, has no antialiased form: gs_api.cpp refuses the flag there)
+    if (a.antialiasing && a.block == 16)
+        hipLaunchKernelGGL((preprocess_kernel<A, B, C, A && B, true>), dim3(blocks), dim3(kPpThreads), 0, s, a, g,
+                           radii, tile_count);
+    else
+        hipLaunchKernelGGL((preprocess_kernel<A, B, C, A && B>), dim3(blocks), dim3(kPpThreads), 0, s, a, g, radii,
+                           tile_count);
 }
 
 void launch_preprocess(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count,

@@ -168,30 +168,24 @@ struct ForwardCall {
     int P, M, W, H, degree;
     float scale_modifier, tan_fovx, tan_fovy;
     bool prefiltered, debug;
+    bool antialiasing = false;  // base forwards only
     void* stream;
 };
 
-Forward6 base_forward(ForwardCall& o) {
-    const int rendered = gs_rasterizer_forward(
+// The base forward; with `maps` also the depth and alpha maps ([1, H, W] each).
+Forward6 base_forward(ForwardCall& o, std::pair<Tensor, Tensor>* maps = nullptr) {
+    if (maps) {
+        maps->first = torch::empty({1, o.H, o.W}, o.out_color.options());
+        maps->second = torch::empty({1, o.H, o.W}, o.out_color.options());
+    }
+    const int rendered = gs_rasterizer_forward_ex(
         buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
         fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
         fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
-        o.prefiltered, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(), o.debug, o.stream);
-    check(rendered, "rasterize_gaussians");
-    return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
-}
-
-// The base forward with the depth and alpha maps ([1, H, W] each, in `maps`).
-Forward6 base_forward_aux(ForwardCall& o, std::pair<Tensor, Tensor>& maps) {
-    maps.first = torch::empty({1, o.H, o.W}, o.out_color.options());
-    maps.second = torch::empty({1, o.H, o.W}, o.out_color.options());
-    const int rendered = gs_rasterizer_forward_aux(
-        buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
-        fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
-        fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
-        o.prefiltered, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(), maps.first.data_ptr<float>(),
-        maps.second.data_ptr<float>(), o.debug, o.stream);
-    check(rendered, "rasterize_gaussians_aux");
+        o.prefiltered, o.antialiasing, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(),
+        maps ? maps->first.data_ptr<float>() : nullptr, maps ? maps->second.data_ptr<float>() : nullptr, o.debug,
+        o.stream);
+    check(rendered, maps ? "rasterize_gaussians_aux" : "rasterize_gaussians");
     return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
 }
 
@@ -268,7 +262,8 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
                         const Tensor& sh_in, int degree, const Tensor& campos_in, bool prefiltered, int foveaStep,
                         const Tensor& out_color_precomp_in, const Tensor& geom_pre, const Tensor& bin_pre,
                         const Tensor& img_pre, bool interpolate_image, bool debug,
-                        std::pair<Tensor, Tensor>* aux_maps = nullptr) {
+                        std::pair<Tensor, Tensor>* aux_maps = nullptr, bool antialiasing = false) {
+    TORCH_CHECK(!(amr && antialiasing), "the AMR rasterizer has no antialiased form");
     if (means3D_in.ndimension() != 2 || means3D_in.size(1) != 3) {
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     }
@@ -313,14 +308,14 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
     o.tan_fovy = tan_fovy;
     o.prefiltered = prefiltered;
     o.debug = debug;
+    o.antialiasing = antialiasing;
     o.stream = stream_of(o.means3D);
     // both forwards write every pixel (the AMR one zeros where it renders
     // nothing) and all radii (the AMR steps >= 1 write their zero radii in
     // the fovea-levels launch)
     o.out_color = torch::empty({3, H, W}, float_opts);
     o.radii = torch::empty({P}, int_opts);
-    if (!amr && aux_maps) return base_forward_aux(o, *aux_maps);
-    if (!amr) return base_forward(o);
+    if (!amr) return base_forward(o, aux_maps);
     return amr_forward(o, background, colors_in, foveaStep, out_color_precomp_in, geom_pre, bin_pre, img_pre,
                        interpolate_image);
 }
@@ -331,12 +326,11 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> RasterizeGaussians(
     const Tensor& scales, const Tensor& rotations, const float scale_modifier, const Tensor& cov3D_precomp,
     const Tensor& viewmatrix, const Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
     const int image_height, const int image_width, const Tensor& sh, const int degree, const Tensor& campos,
-    const bool prefiltered, const bool debug) {
-    Tensor none;
+    const bool prefiltered, const bool debug, const bool antialiasing) {
     auto e = torch::empty({0});
     return rasterize_impl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                           cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                          degree, campos, prefiltered, -1, e, e, e, e, false, debug);
+                          degree, campos, prefiltered, -1, e, e, e, e, false, debug, nullptr, antialiasing);
 }
 
 // RasterizeGaussians plus the depth and alpha maps:
@@ -346,12 +340,12 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> Rasteriz
     const Tensor& scales, const Tensor& rotations, const float scale_modifier, const Tensor& cov3D_precomp,
     const Tensor& viewmatrix, const Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
     const int image_height, const int image_width, const Tensor& sh, const int degree, const Tensor& campos,
-    const bool prefiltered, const bool debug) {
+    const bool prefiltered, const bool debug, const bool antialiasing) {
     auto e = torch::empty({0});
     std::pair<Tensor, Tensor> maps;
     Forward6 f = rasterize_impl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                                sh, degree, campos, prefiltered, -1, e, e, e, e, false, debug, &maps);
+                                sh, degree, campos, prefiltered, -1, e, e, e, e, false, debug, &maps, antialiasing);
     return std::make_tuple(std::get<0>(f), std::get<1>(f), maps.first, maps.second, std::get<2>(f), std::get<3>(f),
                            std::get<4>(f), std::get<5>(f));
 }
@@ -420,7 +414,8 @@ Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, co
                     const float tan_fovy, const Tensor& dL_dout_color_in, const Tensor& sh_in, const int degree,
                     const Tensor& campos_in, const Tensor& geomBuffer, const int R, const Tensor& binningBuffer,
                     const Tensor& imageBuffer, const bool debug, const bool lean,
-                    const Tensor* dL_ddepth_in = nullptr, const Tensor* dL_dalpha_in = nullptr) {
+                    const Tensor* dL_ddepth_in = nullptr, const Tensor* dL_dalpha_in = nullptr,
+                    const std::optional<Tensor>& opacities_in = std::nullopt, const bool antialiasing = false) {
     // (the aux binding: either map's cotangent, [1, H, W], or an empty tensor)
     const bool aux = dL_ddepth_in && dL_dalpha_in && (dL_ddepth_in->numel() != 0 || dL_dalpha_in->numel() != 0);
     const int P = (int)means3D_in.size(0);
@@ -461,7 +456,34 @@ Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, co
         for (const Tensor* bt : {&geomBuffer, &binningBuffer, &imageBuffer})
             require_like(*bt, means3D, "geometry / binning / image buffer", -1, torch::kByte);
         int rc;
-        if (aux) {
+        if (antialiasing) {
+            // the backward of an antialiased forward: the superset entry, whatever else the call is
+            TORCH_CHECK(amr_step == 0, "the AMR rasterizer has no antialiased form");
+            TORCH_CHECK(opacities_in.has_value() && opacities_in->numel() != 0,
+                        "rasterize_gaussians_backward: antialiasing needs the forward's opacities");
+            TORCH_CHECK(!(aux && t_det_backward),
+                        "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
+                        "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
+                        "for this call");
+            const Tensor opac = opacities_in->contiguous();
+            require_like(opac, means3D, "opacities", P);
+            const Tensor dd = aux ? dL_ddepth_in->contiguous() : no_opacity;
+            const Tensor da = aux ? dL_dalpha_in->contiguous() : no_opacity;
+            if (dd.numel()) require_like(dd, means3D, "dL_ddepth", (int64_t)H * W);
+            if (da.numel()) require_like(da, means3D, "dL_dalpha", (int64_t)H * W);
+            Tensor scratch = t_det_backward ? det_scratch(P, R, means3D) : torch::empty({0}, opts);
+            rc = gs_rasterizer_backward_ex(
+                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(opac), fptr(scales),
+                scale_modifier, fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos),
+                tan_fovx, tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
+                fptr(dL_dout), fptr(dd), fptr(da), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
+                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
+                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
+                fptr_mut(dL_drotations), 1, t_det_backward ? 1 : 0,
+                scratch.numel() ? reinterpret_cast<char*>(scratch.data_ptr()) : nullptr, (size_t)scratch.numel(), debug,
+                stream_of(means3D));
+        } else if (aux) {
             TORCH_CHECK(amr_step == 0, "the AMR backward takes no depth / alpha cotangents");
             TORCH_CHECK(!t_det_backward,
                         "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
@@ -527,10 +549,12 @@ Grads8 RasterizeGaussiansBackward(const Tensor& background, const Tensor& means3
                                   const Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
                                   const Tensor& dL_dout_color, const Tensor& sh, const int degree,
                                   const Tensor& campos, const Tensor& geomBuffer, const int R,
-                                  const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug) {
+                                  const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
+                                  const std::optional<Tensor>& opacities, const bool antialiasing) {
     return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, false);
+                        geomBuffer, R, binningBuffer, imageBuffer, debug, false, nullptr, nullptr, opacities,
+                        antialiasing);
 }
 
 // The same, for the autograd wrappers: grad_colors_precomp / grad_cov3Ds_precomp
@@ -541,10 +565,12 @@ Grads8 RasterizeGaussiansBackwardLean(const Tensor& background, const Tensor& me
                                       const Tensor& viewmatrix, const Tensor& projmatrix, const float tan_fovx,
                                       const float tan_fovy, const Tensor& dL_dout_color, const Tensor& sh,
                                       const int degree, const Tensor& campos, const Tensor& geomBuffer, const int R,
-                                      const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug) {
+                                      const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
+                                      const std::optional<Tensor>& opacities, const bool antialiasing) {
     return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, true);
+                        geomBuffer, R, binningBuffer, imageBuffer, debug, true, nullptr, nullptr, opacities,
+                        antialiasing);
 }
 
 // The backward of rasterize_gaussians_aux: the lean binding's arguments with
@@ -560,10 +586,12 @@ Grads8 RasterizeGaussiansBackwardAux(const Tensor& background, const Tensor& mea
                                      const float tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_ddepth,
                                      const Tensor& dL_dalpha, const Tensor& sh, const int degree,
                                      const Tensor& campos, const Tensor& geomBuffer, const int R,
-                                     const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug) {
+                                     const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
+                                     const std::optional<Tensor>& opacities, const bool antialiasing) {
     return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
                         cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, kLean, &dL_ddepth, &dL_dalpha);
+                        geomBuffer, R, binningBuffer, imageBuffer, debug, kLean, &dL_ddepth, &dL_dalpha, opacities,
+                        antialiasing);
 }
 
 // The AMR backward (an extension: the reference's is unreachable): the
@@ -1115,12 +1143,34 @@ void ActivationBackward(const Tensor& d_shs, const Tensor& d_opac, const Tensor&
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X (gfx950) Gaussian rasterizer -- PyTorch binding over include/gsplat_amd.h";
-    m.def("rasterize_gaussians", &RasterizeGaussians);
-    m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward);
-    m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean);
-    m.def("rasterize_gaussians_aux", &RasterizeGaussiansAux);
-    m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux<false>);
-    m.def("rasterize_gaussians_backward_aux_lean", &RasterizeGaussiansBackwardAux<true>);
+    // The reference's positional argument lists, then the antialiasing extension
+    // as trailing arguments with defaults: the forwards take `antialiasing`, the
+    // backwards `opacities` (the forward's input) and `antialiasing`.
+#define GS_FWD_ARGS                                                                                                 \
+    py::arg("background"), py::arg("means3D"), py::arg("colors"), py::arg("opacity"), py::arg("scales"),            \
+        py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"), py::arg("viewmatrix"),           \
+        py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("image_height"),                   \
+        py::arg("image_width"), py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("prefiltered"),        \
+        py::arg("debug"), py::arg("antialiasing") = false
+#define GS_BWD_HEAD                                                                                                 \
+    py::arg("background"), py::arg("means3D"), py::arg("radii"), py::arg("colors"), py::arg("scales"),              \
+        py::arg("rotations"), py::arg("scale_modifier"), py::arg("cov3D_precomp"), py::arg("viewmatrix"),           \
+        py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"), py::arg("dL_dout_color")
+#define GS_BWD_TAIL                                                                                                 \
+    py::arg("sh"), py::arg("degree"), py::arg("campos"), py::arg("geomBuffer"), py::arg("R"),                       \
+        py::arg("binningBuffer"), py::arg("imageBuffer"), py::arg("debug"), py::arg("opacities") = py::none(),      \
+        py::arg("antialiasing") = false
+    m.def("rasterize_gaussians", &RasterizeGaussians, GS_FWD_ARGS);
+    m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward, GS_BWD_HEAD, GS_BWD_TAIL);
+    m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean, GS_BWD_HEAD, GS_BWD_TAIL);
+    m.def("rasterize_gaussians_aux", &RasterizeGaussiansAux, GS_FWD_ARGS);
+    m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux<false>, GS_BWD_HEAD,
+          py::arg("dL_ddepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
+    m.def("rasterize_gaussians_backward_aux_lean", &RasterizeGaussiansBackwardAux<true>, GS_BWD_HEAD,
+          py::arg("dL_ddepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
+#undef GS_FWD_ARGS
+#undef GS_BWD_HEAD
+#undef GS_BWD_TAIL
     m.def("amr_rasterize_gaussians_backward", &AmrRasterizeGaussiansBackward);
     m.def("set_deterministic_backward", [](bool on) { t_det_backward = on; });
     m.def("get_deterministic_backward", []() { return t_det_backward; });

@@ -115,10 +115,20 @@ def gather_view_records(record: torch.Tensor, group=None) -> torch.Tensor:
     return out.view(world * v, n)
 
 
+def refuse_antialiasing(settings, who: str) -> None:
+    """The view records carry dL/d(conic_opacity.w) of a plain forward and the
+    multi-view backward has no antialiased form: an antialiased
+    forward's gradients would be wrong, so the request is refused."""
+    if getattr(settings, "antialiasing", False):
+        raise NotImplementedError(f"{who}: the view exchange has no antialiased form; use the gradient "
+                                  "all-reduce (exchange=\"params\") or turn antialiasing off")
+
+
 def view_record(settings, radii: torch.Tensor, geom: torch.Tensor, num_rendered: int, binning: torch.Tensor,
                 img: torch.Tensor, dL_dpix: torch.Tensor, colors_precomp: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage 1: the blend backward of one rendered view -> its view record."""
     from . import _C
+    refuse_antialiasing(settings, "view_record")
     e = torch.empty(0, device=dL_dpix.device) if colors_precomp is None else colors_precomp
     return _C.rasterize_gaussians_backward_view_grads(
         settings.bg, radii, e, settings.viewmatrix, settings.projmatrix, settings.tanfovx, settings.tanfovy,
@@ -151,6 +161,7 @@ def exchange_view_grads(settings, fwd, dL_dpix: torch.Tensor, means3D: torch.Ten
     chunk c + 1 while the compute stream runs the multi-view backward of
     chunk c (each chunk's work waits only for its own collective), so at
     most one chunk's backward is exposed after the last transfer."""
+    refuse_antialiasing(settings, "exchange_view_grads")
     num_rendered, _color, radii, geom, binning, img = fwd
     rec = view_record(settings, radii, geom, num_rendered, binning, img, dL_dpix)
     return exchange_view_records(rec, settings, means3D, shs, scales, rotations, group, stats, chunks)

@@ -133,13 +133,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         s = raster_settings
         args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug)
+                s.campos, s.prefiltered, s.debug, _antialiasing(s))
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call(
             _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
+        # (opacities: read by the antialiased backward only)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
+                              binningBuffer, imgBuffer, opacities)
         # radii (int32) never carries a gradient: without this autograd fills a
         # zero int tensor of P elements for it on every backward (~6 us at 1M)
         ctx.set_materialize_grads(False)
@@ -151,10 +152,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             return (None,) * 9
         s = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
+         imgBuffer, opacities) = ctx.saved_tensors
         args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, sh, s.sh_degree, s.campos,
-                geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
+                geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug, opacities, _antialiasing(s))
         with _DeterministicScope():
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
              grad_scales, grad_rotations) = _call(_C.rasterize_gaussians_backward_lean, args, s.debug,
@@ -183,13 +184,14 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
         s = raster_settings
         args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug)
+                s.campos, s.prefiltered, s.debug, _antialiasing(s))
         num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer = _call(
             _C.rasterize_gaussians_aux, args, s.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
+        # (opacities: read by the antialiased backward only)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
+                              binningBuffer, imgBuffer, opacities)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii)
         return color, radii, depth, alpha
@@ -200,7 +202,7 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
             return (None,) * 9
         s = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
+         imgBuffer, opacities) = ctx.saved_tensors
         aux = grad_depth is not None or grad_alpha is not None
         if aux and deterministic_requested():
             raise RuntimeError(
@@ -212,7 +214,8 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                                          device=means3D.device)
         head = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color)
-        tail = (sh, s.sh_degree, s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug)
+        tail = (sh, s.sh_degree, s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug,
+                opacities, _antialiasing(s))
         with _DeterministicScope():
             if aux:
                 none = grad_out_color.new_empty(0)
@@ -229,7 +232,8 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 grad_rotations, grad_cov3Ds_precomp, None)
 
 
-class GaussianRasterizationSettings(NamedTuple):
+class _ReferenceSettings(NamedTuple):
+    """The reference's settings tuple (base/.../__init__.py:157-169)."""
     image_height: int
     image_width: int
     tanfovx: float
@@ -242,6 +246,46 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+
+
+class GaussianRasterizationSettings(_ReferenceSettings):
+    """The reference's settings tuple plus ``antialiasing`` (an extension: the
+    reference predates the upstream rasterizer's switch), given as a trailing
+    positional or a keyword argument, default ``False``.  With it each Gaussian
+    is blended with ``opacity * sqrt(max(0.000025, det S / det (S + 0.3 I)))``,
+    ``S`` its 2D covariance before the 0.3-px dilation: the Mip-Splatting 2D
+    filter.
+
+    The tuple itself stays the reference's twelve fields (``_fields``, ``len``,
+    unpacking and ``tuple(settings)`` are unchanged, so it still drops into code
+    written for the reference); the switch is an attribute beside it, kept by
+    ``_replace``.  Code that reads it uses ``getattr(s, "antialiasing", False)``,
+    so the reference's own tuple class is accepted as well."""
+    antialiasing = False
+
+    def __new__(cls, *args, **kw):
+        n = len(_ReferenceSettings._fields)
+        aa = kw.pop("antialiasing", False)
+        if len(args) == n + 1:
+            if "antialiasing" in kw or aa is not False:
+                raise TypeError("GaussianRasterizationSettings: antialiasing given twice")
+            *args, aa = args
+        self = super().__new__(cls, *args, **kw)
+        self.antialiasing = bool(aa)
+        return self
+
+    def _replace(self, **kw):
+        aa = kw.pop("antialiasing", self.antialiasing)
+        out = super()._replace(**kw)
+        out.antialiasing = bool(aa)
+        return out
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", antialiasing={self.antialiasing!r})"
+
+
+def _antialiasing(settings) -> bool:
+    return bool(getattr(settings, "antialiasing", False))
 
 
 def _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp):

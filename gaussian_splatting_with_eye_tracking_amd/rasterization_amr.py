@@ -51,6 +51,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 class _RasterizeGaussians(torch.autograd.Function):
     @classmethod
     def apply(cls, *args):
+        # the settings tuple is the base rasterizer's; its antialiasing switch has
+        # no AMR form: refused rather than rendered without the filter
+        if getattr(args[14], "antialiasing", False):
+            raise NotImplementedError("the AMR (foveated) rasterizer has no antialiased form: use the base "
+                                      "rasterizer, or build the settings with antialiasing=False")
         # the copies of the foveaStep >= 1 interpolation (the reference's racy
         # precomp-copy path) have no backward here: refuse at the call that
         # would record them (grad mode on, an input requiring grad), not at

@@ -33,7 +33,8 @@ def _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_c
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
         scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
         projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
+        campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug,
+        antialiasing=bool(getattr(pipe, "antialiasing", False)))
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
@@ -59,7 +60,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
            starter=None, ender=None, return_aux=False):
     """gaussian_renderer/__init__.py:18-113.  ``return_aux=True`` (an
     extension) adds ``"depth"`` and ``"alpha"``: the differentiable [1, H, W]
-    maps of ``rasterization.rasterize_gaussians_aux`` (depth not normalised)."""
+    maps of ``rasterization.rasterize_gaussians_aux`` (depth not normalised).
+    ``pipe.antialiasing`` (optional, default off) turns the Mip-Splatting 2D
+    filter on (``GaussianRasterizationSettings.antialiasing``)."""
     pts, st, op = _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)
     rasterizer = GaussianRasterizer(raster_settings=st)
     if starter is not None:

@@ -369,12 +369,12 @@ class FlatGaussianModel:
         num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(
             s.bg, xyz, e, a["opacities"], a["scales"], a["rotations"], s.scale_modifier, e, s.viewmatrix,
             s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, a["shs"], s.sh_degree, s.campos,
-            s.prefiltered, s.debug)
+            s.prefiltered, s.debug, bool(getattr(s, "antialiasing", False)))
         out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
         (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = _C.rasterize_gaussians_backward_lean(
             s.bg, xyz, radii, e, a["scales"], a["rotations"], s.scale_modifier, e, s.viewmatrix, s.projmatrix,
             s.tanfovx, s.tanfovy, d_image, a["shs"], s.sh_degree, s.campos, geom, num_rendered, binning, img,
-            s.debug)
+            s.debug, a["opacities"], bool(getattr(s, "antialiasing", False)))
         gv = {g: self.group_view(self.grads, g) for g in GROUPS}
         _C.activation_backward(d_shs, d_opac, d_scales, d_rot, d_means3D, raw["opacity"], raw["scaling"],
                                raw["rotation"], gv["xyz"], gv["f_dc"], gv["f_rest"], gv["opacity"], gv["scaling"],
@@ -395,6 +395,7 @@ def render_and_backward_views(model: FlatGaussianModel, settings: GaussianRaster
     the densification statistics of every rank's view are accumulated too
     (train.py:111-113), so no statistics all-reduce is needed afterwards."""
     from . import data_parallel as DP
+    DP.refuse_antialiasing(settings, "render_and_backward_views")
     s = settings._replace(sh_degree=model.active_sh_degree)
     raw = {g: model.group_view(model.params, g) for g in GROUPS}
     a = model._act

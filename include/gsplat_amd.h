@@ -136,6 +136,52 @@ int gs_rasterizer_backward_aux(int P, int D, int M, int R, const float* backgrou
                                float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
                                float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, void* stream);
 
+/* Antialiasing: the Mip-Splatting 2D filter (no reference counterpart: the
+ * reference predates the switch; the upstream rasterizer's `antialiasing`,
+ * gsplat's rasterize_mode = "antialiased").  Base rasterizer only; an
+ * addition at ABI version 7: no layout and no existing entry changed.
+ *
+ * With antialiasing != 0 the forward blends every Gaussian with the opacity
+ *   opacity * sqrt(max(0.000025, det S / det (S + 0.3 I)))
+ * where S is its 2D covariance before the 0.3-pixel dilation, so the dilation
+ * conserves the splat's energy.  Radii, depths, conics and the tile lists do
+ * not depend on the flag.  Header word 8 of the geometry buffer records the
+ * mode (1 / 0, written by every forward).
+ *
+ * gs_rasterizer_forward_ex is gs_rasterizer_forward with the flag, and
+ * gs_rasterizer_forward_aux when out_depth and out_alpha are both given
+ * (both NULL: no maps).  With antialiasing == 0 it IS those calls.
+ *
+ * gs_rasterizer_backward_ex is the one backward of such a forward: the
+ * arguments of gs_rasterizer_backward_aux (dL_ddepth / dL_dalpha may both be
+ * NULL) plus `opacities` (the forward's input, [P]; read only with the flag),
+ * the flag, and the deterministic form's switch and scratch (deterministic ==
+ * 0: scratch is ignored; deterministic != 0 takes no depth / alpha cotangent).
+ * dL_dopacity is the gradient with respect to the INPUT opacity, and the
+ * coefficient's gradient is part of dL_dmean3D / dL_dcov3D / dL_dscale /
+ * dL_drot.  The flag must be the forward's: a backward whose flag disagrees
+ * with header word 8 -- either way round, the older backward entries
+ * included, which pass 0 -- stores NaNs in the gradients of the visible
+ * Gaussians, and with debug != 0 returns a negative value.  The AMR
+ * rasterizer and the multi-view entries have no antialiased form. */
+int gs_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                             const float* background, int width, int height, const float* means3D, const float* shs,
+                             const float* colors_precomp, const float* opacities, const float* scales,
+                             float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                             const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                             float tan_fovy, int prefiltered, int antialiasing, float* out_color, int* radii,
+                             float* out_depth, float* out_alpha, int debug, void* stream);
+int gs_rasterizer_backward_ex(int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp,
+                              const float* opacities, const float* scales, float scale_modifier,
+                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                              const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                              const float* dL_dpix, const float* dL_ddepth, const float* dL_dalpha, float* dL_dmean2D,
+                              float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                              float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
+                              int deterministic, char* scratch, size_t scratch_bytes, int debug, void* stream);
+
 /* Data-parallel training (no reference counterpart: the
  * reference trains one view per step on one GPU, train.py:67-125).
  *
