@@ -1,0 +1,419 @@
+"""The HIP kernels against the oracle on general views (gs_helpers.general_case).
+
+Every other parity test renders through the identity camera (or a few degrees
+of yaw) a scene that lies wholly in front of it and inside the frustum.  Here
+the camera has a full rotation and a translation, and the scene has Gaussians
+behind the camera and inside the near cull (z <= 0.2), just in front of it
+(radii beyond the image: the tile rectangle clamped on all four sides),
+outside the 1.3 tan(fov) clamp of t.x/t.z, t.y/t.z (the clamp branch of the
+cov2D backward) and with alpha at its 0.99 clamp; every test asserts on the
+case's census that it does.  The oracle itself is held to a float64 autograd
+restatement on these cases in test_oracle_autograd.py.
+
+The bars are the project's: integer buffers and preprocess floats bit-exact,
+image L1 < 1e-5, gradients within 1e-4 relative (L2) and the element-wise bar
+with oracle.grad_allowance.
+
+Antialiasing is checked with general_case(clamp=False) only: its reference
+(antialias_reference.coef64) takes no 1.3 tan(fov) clamp, so antialiasing
+together with an active clamp stays untested.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import antialias_reference as AR
+import aux_reference as AXR
+import gs_helpers as G
+import oracle as O
+from gaussian_splatting_with_eye_tracking_amd import synthetic as S
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
+         "dL_drotations"]
+# (P, W, H, seed, log_scale_mean)
+CASES = {
+    "g400_64x48": (400, 64, 48, 5, G.GENERAL_LOG_SCALE),
+    "g600_80x64": (600, 80, 64, 7, G.GENERAL_LOG_SCALE),
+    "g3k_250x130": (3000, 250, 130, 7, G.GENERAL_LOG_SCALE_LARGE),  # ragged tiles, longer tile lists
+}
+AMR_CASE = (1500, 224, 160, 5, G.GENERAL_LOG_SCALE_LARGE)
+VARIANTS = ["sh", "colors_precomp", "cov3D_precomp"]
+BG = (0.2, 0.1, 0.05)
+
+
+def _C():
+    import gaussian_splatting_with_eye_tracking_amd._C as C
+    return C
+
+
+def _TP():
+    import test_gpu_parity as TP
+    return TP
+
+
+# ------------------------------------------------------------ shared references
+@functools.lru_cache(maxsize=None)
+def _case(name, variant="sh"):
+    """Inputs of one case (built once, never modified)."""
+    P, W, H, seed, lsm = CASES[name]
+    sc, cam, dpix = G.general_case(P, W, H, seed, log_scale_mean=lsm)
+    colors = cov = None
+    if variant == "colors_precomp":
+        colors = np.random.default_rng(seed + 5).uniform(0, 1, (P, 3)).astype(np.float32)
+    if variant == "cov3D_precomp":
+        _, r0, _ = _TP()._oracle_forward(sc, cam)
+        cov = r0.cov3D.copy()
+        cov[r0.radii <= 0] = np.array([1e-4, 0, 0, 1e-4, 0, 1e-4], np.float32)  # (never computed: a valid one)
+    return dict(P=P, W=W, H=H, seed=seed, sc=sc, cam=cam, colors=colors, cov=cov, dpix=dpix)
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name, variant="sh"):
+    """The oracle's forward, gradients, allowance and census of one case
+    (computed once, left unchanged)."""
+    c = _case(name, variant)
+    os_, ref, kw = _TP()._oracle_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
+    rg = O.backward(os_, ref, c["sc"].means3D, c["dpix"], **kw)
+    al, ties = O.grad_allowance(os_, ref, c["sc"].means3D, c["dpix"], parts=True, **kw)
+    census = G.general_case_census(c["sc"], c["cam"], ref, rg)
+    return dict(s=os_, fwd=ref, kw=kw, rg=rg, al=al, ties=ties, census=census)
+
+
+def _covered(name, variant="sh"):
+    """The coverage conditions of the case: asserted by every test using it."""
+    c, o = _case(name, variant), _oracle(name, variant)
+    G.assert_general_coverage(o["census"], c["W"], c["H"])
+    return c, o
+
+
+def _forward(c, bg=BG):
+    return _TP()._gpu_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=bg)
+
+
+def _backward(c, fwd, det=False, lean=False):
+    import test_gpu_deterministic_backward as TD
+    return TD._backward(c, fwd, det, lean=lean)
+
+
+def _assert_grads(case, grads, c, o):
+    rg = o["rg"]
+    for n, g in zip(NAMES, grads):
+        gg = g.cpu().numpy()
+        assert gg.shape == rg[n].shape, n
+        assert np.all(np.isfinite(gg)), n
+        err = G.rel_err(gg, rg[n])
+        print(f"{case} {n}: rel_err {err:.3e}")
+        assert err < G.GRAD_REL_TOL, (n, err)
+    G.assert_grads_elementwise(case, NAMES, grads, rg, c["sc"], c["cam"], o["fwd"], allow=o["al"], ties=o["ties"])
+
+
+# ------------------------------------------------------------------ 1. forward
+@pytest.mark.parametrize("name", list(CASES))
+def test_forward_buffers_bit_exact(name):
+    C = _C()
+    c, o = _covered(name)
+    ref, census = o["fwd"], o["census"]
+    P, W, H = c["P"], c["W"], c["H"]
+    C.set_thread_option("store_cov3d", 1)  # the geometry buffer's cov3D is written on request only
+    try:
+        _, _, (K, color, radii, geom, binning, img) = _forward(c)
+    finally:
+        C.set_thread_option("store_cov3d", 0)
+    assert K == ref.num_rendered
+    d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
+    got_radii = radii.cpu().numpy()
+    np.testing.assert_array_equal(got_radii, ref.radii)
+    # behind the camera or inside the near cull: no radius, no tile
+    assert not got_radii[census["near_culled_mask"]].any() and not got_radii[census["behind_mask"]].any()
+    touched = d["tiles_touched"].cpu().numpy().astype(np.uint32)
+    assert not touched[census["near_culled_mask"]].any()
+    vis = ref.radii > 0
+    for k, want in (("depths", ref.depths), ("means2D", ref.means2D), ("conic_opacity", ref.conic_opacity),
+                    ("rgb", ref.rgb), ("cov3D", ref.cov3D)):
+        np.testing.assert_array_equal(d[k].cpu().numpy()[vis], want[vis], err_msg=k)
+    np.testing.assert_array_equal(d["clamped_bits"].cpu().numpy()[vis],
+                                  (ref.clamped[vis] * np.array([1, 2, 4], np.uint8)).sum(1))
+    np.testing.assert_array_equal(touched, ref.tiles_touched)
+    # a radius beyond the image: the rectangle is the whole grid
+    assert touched.max() == ((W + 15) // 16) * ((H + 15) // 16)
+    np.testing.assert_array_equal(d["ranges"].cpu().numpy().astype(np.uint32), ref.ranges)
+    np.testing.assert_array_equal(d["point_list"].cpu().numpy().astype(np.uint32), ref.point_list)
+    np.testing.assert_array_equal(d["point_list_keys"].cpu().numpy().view(np.uint64), ref.point_list_keys)
+    l1 = G.image_l1(color.cpu().numpy(), ref.color)
+    ncont = d["n_contrib"].cpu().numpy().astype(np.uint32)
+    miss = float(np.mean(ncont != ref.n_contrib))
+    l1t = G.image_l1(d["accum_alpha"].cpu().numpy(), ref.final_T)
+    print(f"{name}: image L1 {l1:.3e}, n_contrib mismatch {miss:.3e}, final T L1 {l1t:.3e}")
+    assert l1 < G.IMAGE_L1_TOL
+    assert miss < 1e-3  # exp is hardware v_exp_f32 vs libm expf
+    assert l1t < G.IMAGE_L1_TOL
+
+
+# ----------------------------------------------------------------- 2. backward
+# every blend pairing; the coefficient form of the SH backward (sh_drgb 0) where there are SH
+_BACKWARD = [(n, v, f, b, 1) for n in CASES for v in VARIANTS for f in (0, 1) for b in (0, 1)] + \
+            [(n, "sh", f, b, 0) for n in CASES for f in (0, 1) for b in (0, 1)]
+
+
+@pytest.mark.parametrize("name,variant,fwd_variant,bwd_variant,sh_drgb", _BACKWARD)
+def test_backward_parity(name, variant, fwd_variant, bwd_variant, sh_drgb):
+    C = _C()
+    c, o = _covered(name, variant)
+    try:
+        C.set_tuning("fwd_variant", fwd_variant)
+        C.set_tuning("bwd_variant", bwd_variant)
+        C.set_thread_option("sh_drgb", sh_drgb)
+        fwd = _forward(c)
+        grads = _backward(c, fwd)
+        lean = _backward(c, fwd, lean=True)
+    finally:
+        C.set_tuning("fwd_variant", -1)
+        C.set_tuning("bwd_variant", -1)
+        C.set_thread_option("sh_drgb", 1)
+    assert G.image_l1(fwd[2][1].cpu().numpy(), o["fwd"].color) < G.IMAGE_L1_TOL
+    _assert_grads(f"general_{name}_{variant}_f{fwd_variant}b{bwd_variant}d{sh_drgb}", grads, c, o)
+    # the autograd wrappers' binding: colour / covariance gradients only when
+    # their precomputed input was given, the others within float-atomic noise
+    for n, g, gl in zip(NAMES, grads, lean):
+        if (n == "dL_dcolors" and c["colors"] is None) or (n == "dL_dcov3D" and c["cov"] is None):
+            assert gl.numel() == 0, n
+        else:
+            assert G.rel_err(gl.cpu().numpy(), g.cpu().numpy()) < 1e-5, n
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_deterministic_backward(name):
+    c, o = _covered(name)
+    fwd = _forward(c)
+    d1 = _backward(c, fwd, det=True)
+    d2 = _backward(c, _forward(c), det=True)
+    _assert_grads(f"general_deterministic_{name}", d1, c, o)
+    for n, x, y in zip(NAMES, d1, d2):
+        assert torch.equal(x, y), n
+
+
+# -------------------------------------------------------------- 3. aux outputs
+@functools.lru_cache(maxsize=None)
+def _aux_reference(name):
+    c = _case(name)
+    kw = dict(shs=c["sc"].shs, scales=c["sc"].scales, rotations=c["sc"].rotations)
+    return AXR.reference_forward(c["cam"], c["sc"].means3D, c["sc"].opacities, kw, bg=BG)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_aux_outputs(name):
+    """Depth and alpha maps and their backward: the depth's pull-back onto the
+    means is dL_dz V[:3, 2], no longer (0, 0, 1)."""
+    import test_gpu_aux_outputs as TX
+    C = _C()
+    c, o = _covered(name)
+    ref = _aux_reference(name)
+    zaxis = np.asarray(c["cam"].world_view_transform, np.float64)[:3, 2]
+    assert np.abs(zaxis).min() > 0.2  # every component of the pull-back matters
+    s, t, sh, col = TX._operands(c["sc"], c["cam"], "sh", c["seed"], bg=BG)
+    K, color, depth, alpha, radii, geom, binning, img = TX._forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    assert K == ref["fwd"].num_rendered
+    zmax = float(ref["fwd"].depths[ref["fwd"].radii > 0].max())
+    l1a = G.image_l1(alpha.cpu().numpy(), ref["alpha"])
+    l1d = G.image_l1(depth.cpu().numpy(), ref["depth"])
+    print(f"{name}: alpha L1 {l1a:.3e}, depth L1 {l1d:.3e} (bar {G.IMAGE_L1_TOL * zmax:.3e}, max z {zmax:.3f})")
+    assert G.image_l1(color.cpu().numpy(), ref["fwd"].color) < G.IMAGE_L1_TOL
+    assert l1a < G.IMAGE_L1_TOL
+    assert l1d < G.IMAGE_L1_TOL * zmax  # the blend is linear in the feature
+    dpix, dd, da = TX._cotangents(c["W"], c["H"], c["seed"])
+    grads = TX._backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
+    TX._check_against_reference(f"general_aux_{name}", grads, ref, c["sc"], c["cam"], dpix, dd, da)
+    # the depth cotangent alone
+    grads = TX._backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, None, dd, None)
+    TX._check_against_reference(f"general_aux_depth_{name}", grads, ref, c["sc"], c["cam"], None, dd, None)
+
+
+# ----------------------------------------------------------------------- 4. AMR
+@functools.lru_cache(maxsize=None)
+def _amr_case():
+    P, W, H, seed, lsm = AMR_CASE
+    sc, cam, dpix = G.general_case(P, W, H, seed, log_scale_mean=lsm)
+    s = O.settings_from_camera(cam)
+    kw = dict(means3D=sc.means3D, opacities=sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
+    fwd32 = O.forward(s, sc.means3D, sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations, block=32)
+    rg32 = O.backward(s, fwd32, sc.means3D, dpix, shs=sc.shs, scales=sc.scales, rotations=sc.rotations, block=32)
+    return dict(P=P, W=W, H=H, seed=seed, sc=sc, cam=cam, dpix=dpix, s=s, kw=kw,
+                census=G.general_case_census(sc, cam, fwd32, rg32))
+
+
+def _amr_covered():
+    a = _amr_case()
+    G.assert_general_coverage(a["census"], a["W"], a["H"])
+    return a
+
+
+def _amr_render_once(a, interpolate, requires_grad=False):
+    from diff_gaussian_rasterization_amr import GaussianRasterizer
+    s = G.torch_settings(a["cam"], amr=True)
+    t = G.scene_tensors(a["sc"], requires_grad=requires_grad)
+    m2 = torch.zeros_like(t["means3D"], requires_grad=requires_grad)
+    color, radii, gb, bb, ib = GaussianRasterizer(s)(
+        means3D=t["means3D"], means2D=m2, opacities=t["opacities"], shs=t["shs"], scales=t["scales"],
+        rotations=t["rotations"], foveaStep=-2, interpolate_image=interpolate)
+    torch.cuda.synchronize()
+    return t, m2, color, radii, (gb, bb, ib)
+
+
+@pytest.mark.parametrize("amr_variant", [4, 0])
+@pytest.mark.parametrize("interpolate", [False, True])
+def test_amr_render_once(interpolate, amr_variant):
+    C = _C()
+    a = _amr_covered()
+    P, W, H = a["P"], a["W"], a["H"]
+    C.set_tuning("amr_variant", amr_variant)
+    try:
+        with torch.no_grad():
+            _, _, color, radii, (gb, bb, ib) = _amr_render_once(a, interpolate)
+    finally:
+        C.set_tuning("amr_variant", 4)
+    rcol, rrad, st = O.amr_forward(a["s"], foveaStep=-2, interpolate_image=interpolate, **a["kw"])
+    np.testing.assert_array_equal(radii.cpu().numpy(), rrad)
+    assert not rrad[a["census"]["near_culled_mask"]].any()
+    K = st.fwd.num_rendered
+    d = C.parse_buffers(gb, bb, ib, P, K, W, H, 32)
+    assert int(d["hdr"][0].item()) == K
+    np.testing.assert_array_equal(d["ranges"].cpu().numpy().astype(np.uint32), st.fwd.ranges)
+    np.testing.assert_array_equal(d["point_list"].cpu().numpy().astype(np.uint32), st.fwd.point_list)
+    np.testing.assert_array_equal(d["pv"].cpu().numpy()[:3].astype(np.uint32), st.percentile_values)
+    np.testing.assert_array_equal(d["levels"].cpu().numpy().astype(np.uint32), st.levels)
+    assert len(set(np.minimum(st.levels, 4).tolist())) > 1  # several levels in play
+    l1 = G.image_l1(color.cpu().numpy(), rcol)
+    print(f"amr general interpolate={interpolate} variant={amr_variant}: image L1 {l1:.3e}")
+    assert l1 < G.IMAGE_L1_TOL
+
+
+@pytest.mark.parametrize("interpolate", [False, True])
+def test_amr_backward(interpolate):
+    C = _C()
+    a = _amr_covered()
+    P, W, H = a["P"], a["W"], a["H"]
+    t, m2, color, radii, (gb, bb, ib) = _amr_render_once(a, interpolate, requires_grad=True)
+    (color * torch.from_numpy(a["dpix"]).cuda()).sum().backward()
+    torch.cuda.synchronize()
+    K = int(C.parse_buffers(gb, bb, ib, P, 0, W, H, 32)["hdr"][0].item())
+    levels = C.parse_buffers(gb, bb, ib, P, K, W, H, 32)["levels"].cpu().numpy().astype(np.uint32)
+    rg = O.amr_backward(a["s"], a["kw"], a["dpix"], -2, levels, interpolate_image=interpolate)
+    assert np.abs(rg["dL_dopacity"]).sum() > 0  # the case has gradient at all
+    for n, g in (("dL_dmeans2D", m2.grad), ("dL_dmeans3D", t["means3D"].grad), ("dL_dsh", t["shs"].grad),
+                 ("dL_dopacity", t["opacities"].grad), ("dL_dscales", t["scales"].grad),
+                 ("dL_drotations", t["rotations"].grad)):
+        gg = g.cpu().numpy()
+        assert np.all(np.isfinite(gg)), n
+        err = G.rel_err(gg, rg[n])
+        print(f"amr general backward interpolate={interpolate} {n}: rel_err {err:.3e}")
+        assert err < G.GRAD_REL_TOL, (n, err)
+
+
+# ---------------------------------------------------------------- 5. multi-view
+MV_NAMES = ("dL_dmeans3D", "dL_dsh", "dL_dopacity", "dL_dscales", "dL_drotations")
+
+
+@functools.lru_cache(maxsize=None)
+def _multiview_reference(name):
+    """The per-view oracle backwards of the case's scene seen from the two
+    general views and the identity view, summed in float64."""
+    c = _case(name)
+    sc = c["sc"]
+    kw = dict(shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
+    cams = [G.general_camera(c["W"], c["H"], v) for v in ("a", "b", "identity")]
+    total, allow, vis = {}, {}, []
+    for v, cam in enumerate(cams):
+        s = O.settings_from_camera(cam)
+        dpix = S.make_cotangent(c["H"], c["W"], 10 + v)
+        fwd = O.forward(s, sc.means3D, sc.opacities, **kw)
+        rg = O.backward(s, fwd, sc.means3D, dpix, **kw)
+        al, _ = O.grad_allowance(s, fwd, sc.means3D, dpix, **kw)
+        for n in MV_NAMES:
+            total[n] = rg[n].astype(np.float64) + total.get(n, 0.0)
+            allow[n] = np.asarray(al[n], np.float64) + allow.get(n, 0.0)
+        vis.append(fwd.radii > 0)
+    z = [G.view_space(sc.means3D, cam)[:, 2] for cam in cams]
+    return cams, total, allow, vis, z
+
+
+@pytest.mark.parametrize("name", ["g400_64x48", "g3k_250x130"])
+def test_multiview_equals_sum_of_oracle_view_backwards(name):
+    """A Gaussian behind one camera and in front of another takes the
+    gradient of the views that see it alone (present[])."""
+    from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
+    C = _C()
+    c, _ = _covered(name)
+    cams, want, allow, vis, z = _multiview_reference(name)
+    mixed = np.zeros(c["P"], bool)
+    for i in range(len(cams)):
+        for j in range(len(cams)):
+            mixed |= (z[i] < 0) & vis[j]
+    print(f"{name}: {int(mixed.sum())} Gaussians behind one camera and rendered by another")
+    assert int(mixed.sum()) >= 20
+    t = G.scene_tensors(c["sc"])
+    e = torch.Tensor([])
+    records = []
+    for v, cam in enumerate(cams):
+        s = G.torch_settings(cam)
+        dpix = torch.from_numpy(S.make_cotangent(c["H"], c["W"], 10 + v)).cuda()
+        K, color, radii, geom, binning, img = C.rasterize_gaussians(
+            s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e, s.viewmatrix, s.projmatrix,
+            s.tanfovx, s.tanfovy, s.image_height, s.image_width, t["shs"], 3, s.campos, False, False)
+        np.testing.assert_array_equal(radii.cpu().numpy() > 0, vis[v])
+        records.append(DP.view_record(s, radii, geom, K, binning, img, dpix))
+    got = DP.multiview_param_grads(torch.stack(records), t["means3D"], t["shs"], 3, t["scales"], t["rotations"], 1.0)
+    torch.cuda.synchronize()
+    seen = np.logical_or.reduce(vis)
+    for n, g in zip(MV_NAMES, got):
+        gg = g.cpu().numpy().reshape(want[n].shape)
+        assert np.all(np.isfinite(gg)), n
+        assert not gg[~seen].any(), n  # rendered by no view: no gradient
+        err = G.rel_err(gg, want[n])
+        print(f"multiview {name} {n}: rel_err {err:.3e}")
+        assert err < G.GRAD_REL_TOL, (n, err)
+    G.assert_grads_elementwise(f"general_multiview_{name}", MV_NAMES, [g.reshape(want[n].shape) for n, g in
+                                                                        zip(MV_NAMES, got)], want, allow=allow)
+
+
+# -------------------------------------------------------------- 6. antialiasing
+@functools.lru_cache(maxsize=None)
+def _antialias_reference(name, variant):
+    import test_gpu_antialiasing as TA
+    P, W, H, seed, lsm = CASES[name]
+    sc, cam, dpix = G.general_case(P, W, H, seed, clamp=False, log_scale_mean=lsm)
+    kw, deg = TA._variant_kw(sc, variant, seed)
+    ref = AR.reference_forward(cam, sc.means3D, sc.opacities, kw, sh_degree=deg)
+    t64 = lambda a: torch.tensor(np.asarray(a, np.float64))  # noqa: E731
+    _, _, inside, _ = AR.coef64(cam, t64(sc.means3D), t64(sc.scales), t64(sc.rotations))
+    return sc, cam, dpix, kw, deg, ref, inside, AR.reference_backward(ref, dpix), AR.reference_allowance(ref, dpix)
+
+
+@pytest.mark.parametrize("variant", ["sh", "colors", "cov"])
+@pytest.mark.parametrize("name", ["g400_64x48", "g3k_250x130"])
+def test_antialiasing(name, variant):
+    """The antialiased forward and backward under the general camera, on the
+    scene that needs no clamp (the reference takes none)."""
+    import test_gpu_antialiasing as TA
+    C = _C()
+    sc, cam, dpix, kw, deg, ref, inside, rg, al = _antialias_reference(name, variant)
+    fwd = ref["fwd"]
+    vis = fwd.radii > 0
+    assert vis.sum() >= 0.9 * vis.size and inside[vis].all()
+    assert not G.clamp_active(sc.means3D, cam)[vis].any()
+    s, t = TA._operands(sc, cam, kw, deg, True)
+    K, color, radii, geom, binning, img = TA._forward(C, s, t)
+    assert K == fwd.num_rendered and np.array_equal(radii.cpu().numpy(), fwd.radii)
+    P, W, H = sc.means3D.shape[0], cam.image_width, cam.image_height
+    d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
+    co = d["conic_opacity"].cpu().numpy()
+    assert np.array_equal(TA._bits(co[vis, 3]), TA._bits(ref["o_eff"][vis, 0]))
+    assert np.array_equal(TA._bits(co[vis, :3]), TA._bits(fwd.conic_opacity[vis, :3]))
+    l1 = G.image_l1(color.cpu().numpy(), fwd.color)
+    print(f"antialias general {name} {variant}: image L1 {l1:.3e}")
+    assert l1 < G.IMAGE_L1_TOL
+    grads = TA._backward(C, s, t, radii, geom, K, binning, img, dpix)
+    TA._check_grads(f"general_antialias_{name}_{variant}", grads, rg, al, sc, cam, fwd)
