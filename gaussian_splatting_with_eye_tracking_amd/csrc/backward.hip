@@ -1,6 +1,6 @@
 // backward.hip -- gradients on gfx950.
 //
-// render_bwd_kernel follows base/cr/backward.cu:399-557 (renderCUDA
+// render_bwd_kernel (gs_blend_bwd.cuh, launched here) follows base/cr/backward.cu:399-557 (renderCUDA
 // backward): per pixel, back-to-front replay from n_contrib with the same
 // T/accum_rec recurrences and the same nine per-(pixel, Gaussian) gradient
 // terms.  What changes is where the sums go: the reference issues 9 global
@@ -15,8 +15,9 @@
 //      9 s + q = value q of slot s), forms the reference's nine terms and adds
 //      them into grad_accum[P][kGradRow] -- one atomic instruction per 7
 //      (tile, Gaussian) pairs.
-// (The fallback form sums by a full transposition into LDS rows and flushes
-// one 64-B atomic row per (tile, Gaussian) at the end of each batch.)
+// (render_bwd_rows_kernel -- the fallback, AMR, deterministic and aux
+// backwards -- sums by a full transposition into LDS rows and flushes one 64-B
+// atomic row per (tile, Gaussian) at the end of each batch.)
 // The backward also starts each tile at max(n_contrib) of its pixels
 // (recorded by the forward) instead of the end of the range: entries past it
 // are skipped by every pixel in the reference too.
@@ -27,630 +28,17 @@
 // reference's dL_dmeans2D / dL_dconic / dL_dopacity / dL_dcolors layout from
 // grad_accum, and writes every output element (zeros included).
 #include <algorithm>
-#include <type_traits>
 
 #include <hip/hip_ext.h>
 
 #include "gs_blend.cuh"
+#include "gs_blend_bwd.cuh"
 #include "gs_bwd_math.cuh"
 #include "gs_device.cuh"
 #include "gs_kernels.h"
 
 namespace gsamd {
 
-constexpr int kNG = 9;      // gradient terms per (pixel, Gaussian)
-static_assert(kDetRow == kNG, "the deterministic backward's partial rows hold the nine terms");
-constexpr int kAccRow = 9;   // LDS accumulator row (floats; odd stride: 9 scalar stores per row)
-constexpr int kPPL = 4;      // pixels per lane: one wave64 covers the 16x16 tile (gs_blend.cuh mapping)
-static_assert(kAuxDz == kAccRow && kAuxDz < kGradRow, "the aux backward's tenth sum takes a spare float of the row");
-
-// One 16x16 tile per single-wave workgroup, 4 pixels per lane (lane l: column
-// l % 16 of the 4 row groups).  kSel (the default): the select-form visit
-// with SGPR-mask selects and per-batch compare sets, staged transposed sums
-// and the flush fused into the staging reduce (below).  !kSel (the fallback,
-// and the AMR backward): the predicate form, full sums by transposition into
-// LDS rows, one 64-B atomic row per (tile, Gaussian) at the end of each batch.
-// kDet (the deterministic backward, on the fallback form): grad_accum is the
-// caller's partials array [R][kNG] instead -- the flush stores the nine terms
-// of sorted instance i (= range.x + its index in the tile's list) at row i
-// with plain stores and issues no atomic; reduce_partials_kernel (below) sums
-// each Gaussian's rows in a fixed order.  Every row below min(n,
-// max_contrib[tile]) is written (zeros where the default flush adds nothing),
-// the rows at or past it are never read.
-// kAux (the depth / alpha maps' backward, on the fallback form): depth and
-// alpha are two more blend channels with features (z, 1), background (0, 0)
-// and cotangents dL_ddepth / dL_dalpha (either may be null, as dL_dpixels
-// then: zeros) replayed in the same walk -- dL/dalpha of every pair gains
-// their terms, and a tenth per-Gaussian sum dL/dz = sum alpha T dL_ddepth
-// goes to float kAuxDz of the Gaussian's grad_accum row (LDS rows of 10).
-// (a template parameter, as kAMR: run-time branches cost the base kernel 12 %)
-template <bool kSel, bool kAMR = false, bool kOpT = false, bool kDet = false, bool kAux = false>
-__global__ void __launch_bounds__(64, 4) render_bwd_kernel(
-    int W, int H, const uint32_t* __restrict__ ranges, const uint32_t* __restrict__ max_contrib,
-    const uint32_t* __restrict__ point_list, const float2* __restrict__ means2D,
-    const float4* __restrict__ conic_opacity, const float* __restrict__ colors, const float* __restrict__ final_Ts,
-    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels, const float* __restrict__ bg,
-    float* __restrict__ grad_accum, int cull, int gx, int amr_mode, const uint32_t* __restrict__ levels,
-    const uint32_t* __restrict__ bucket_count, const uint32_t* __restrict__ bucket_list,
-    const uint32_t* __restrict__ hdr, const float* __restrict__ depths, const float* __restrict__ dL_ddepth,
-    const float* __restrict__ dL_dalpha_map) {
-#pragma clang fp contract(fast)
-    static_assert(!(kSel && kAMR), "the AMR backward is the fallback form");
-    static_assert(!kAux || (!kSel && !kAMR && !kDet), "the aux backward is the base fallback form");
-    constexpr int kRow = kAux ? kAccRow + 1 : kAccRow;  // LDS accumulator row of this form
-    static_assert(!kDet || (!kSel && !kAMR), "the deterministic backward is the base fallback form");
-    constexpr int kB = 64;  // Gaussians per LDS batch
-    __shared__ uint32_t s_id[2][kB];  // double-buffered: the next batch's ids land while this one flushes
-    // (x, y, r, g) and the scaled conic / opacity as two b128 reads, b as one
-    // b32 (LDS cycles per wave-read: b128 4, b96 8, b64 / b32 2)
-    __shared__ float4 s_a[kB];
-    __shared__ float4 s_co[kB];
-    // (b at a 16-B stride: one LDS address serves all three record reads)
-    __shared__ float4 s_b[kB];
-    // !kSel: per-Gaussian sums, one row per batch slot, flushed per batch
-    __shared__ float s_acc[kSel ? 1 : kB * kRow];
-    __shared__ uint64_t s_bal[4];
-    // kSel: the per-Gaussian sums are finished in groups of 7 Gaussians --
-    // each visit parks its two transposed registers (16 column partials of
-    // each of 8 values, swap_rows8_pk_t) in a staging slot, and one pass over
-    // 7 slots sums them with 63 lanes at once (lane = 9 * slot + value)
-    // instead of 14 DPP adds per Gaussian.  Layout: reduce lane l's 16
-    // partials are 4 float4s at l * 4 + i * kStagePitch (i = 0..3), so each
-    // b128 read is 64 consecutive dwords per 16 lanes; the pitch's 16-float pad
-    // spreads the writers' 4 column groups over all 64 banks.
-    constexpr int kStageSlots = 7;
-    constexpr int kStagePitch = 272;
-    __shared__ __attribute__((aligned(16))) float s_stage[kSel ? 3 * kStagePitch + 256 : 1];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    // AMR mode (kAMR, amr_mode != 0; the foveated backward, an extension beyond
-    // parity): block b = (32-px tile b / 4, sub-lattice (b & 1, (b >> 1) & 1)),
-    // its 16 x 16 pixels at stride 2 -- the pixels amr_render_kernel blended
-    // for that AMR round.  amr_mode = k > 0: foveaStep k's image (round k of
-    // tiles with level >= k); < 0: render_once (rounds <= level).
-    int tile;
-    uint32_t ox, oy;
-    // (a template parameter: run-time AMR branches cost the base kernel 12 %)
-    constexpr uint32_t pstride = kAMR ? 2 : 1;
-    if constexpr (kAMR) {
-        tile = (int)(blockIdx.x >> 2);
-        const uint32_t sx = blockIdx.x & 1u, sy = (blockIdx.x >> 1) & 1u;
-        const uint32_t round = sx == 0 ? (sy == 0 ? 1u : 4u) : (sy == 0 ? 3u : 2u);  // amr/cr/forward.cu:313-339
-        const uint32_t L = min(levels[tile], 4u);
-        if (amr_mode > 0 ? (round != (uint32_t)amr_mode || L < round) : round > L) return;
-        ox = (uint32_t)(tile % gx) * 32 + sx;
-        oy = (uint32_t)(tile / gx) * 32 + sy;
-    } else {
-        tile = (int)blockIdx.x;
-        if (bucket_count) {
-            // rank blockIdx.x of the heaviest-first order: the bucket whose
-            // inclusive count first exceeds it (256 buckets: 4 per lane)
-            const uint4 c4 = reinterpret_cast<const uint4*>(bucket_count)[lane];
-            const uint32_t c = c4.x + c4.y + c4.z + c4.w;
-            uint32_t incl = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = (uint32_t)__shfl_up((int)incl, d, 64);
-                if (lane >= d) incl += y;
-            }
-            const uint32_t rank = blockIdx.x;
-            const uint64_t past = __ballot(incl > rank);
-            // counts that do not cover the grid exactly (an image buffer whose
-            // base forward render did not fill the buckets, e.g. from another
-            // caller or size): every block takes the identity order instead,
-            // so each tile is still processed exactly once
-            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            if (total == gridDim.x && past != 0ull) {
-                const int L = __builtin_ctzll(past);
-                uint32_t r = rank - (uint32_t)__builtin_amdgcn_readlane((int)(incl - c), L);
-                const uint32_t q0 = (uint32_t)__builtin_amdgcn_readlane((int)c4.x, L),
-                               q1 = (uint32_t)__builtin_amdgcn_readlane((int)c4.y, L),
-                               q2 = (uint32_t)__builtin_amdgcn_readlane((int)c4.z, L);
-                int b = 4 * L;
-                if (r >= q0) { r -= q0; b++;
-                    if (r >= q1) { r -= q1; b++;
-                        if (r >= q2) { r -= q2; b++; } } }
-                tile = (int)bucket_list[(size_t)b * gridDim.x + r];
-            }
-        }
-        ox = (uint32_t)(tile % gx) * 16;
-        oy = (uint32_t)(tile / gx) * 16;
-    }
-    const uint2 range = reinterpret_cast<const uint2*>(ranges)[tile];
-    const int n = (int)(range.y - range.x);
-    int m = kAMR ? n : min(n, (int)max_contrib[tile]);
-    if (m == 0) return;  // block-uniform
-
-    const PixelSetT<kPPL> px = make_pixels_t<kPPL, 1>(W, H, ox, oy, pstride);
-    const size_t plane = (size_t)H * W;
-    const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
-    // row group k's pixel y is py0 + 4 k stride: exact small-integer floats, the
-    // same operand the forward subtracts (3 fewer live registers than px.y[])
-    const float py0 = px.y[0];
-    // accum_rec . dL_dpix is all the reference's accum_rec / last_color
-    // recurrences (backward.cu:500-507) feed into dL_dalpha, so each pixel
-    // carries that one scalar instead of 2 x 3.
-    float T[kPPL], nbg[kPPL], dpx[kPPL][3], acc_dot[kPPL];
-    float dax[kAux ? kPPL : 1][2];  // kAux: (dL_ddepth, dL_dalpha) of the pixel
-    uint32_t last[kPPL];
-    uint32_t wave_last = 0;
-#pragma unroll
-    for (int k = 0; k < kPPL; k++) {
-        const uint32_t pid = px.pid[k];
-        const float Tf = px.inside[k] ? final_Ts[pid] : 0.f;
-        T[k] = Tf;
-        last[k] = px.inside[k] ? n_contrib[pid] : 0u;
-        wave_last = max(wave_last, last[k]);
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            dpx[k][c] = (px.inside[k] && (!kAux || dL_dpixels)) ? dL_dpixels[c * plane + pid] : 0.f;
-        if constexpr (kAux) {
-            dax[k][0] = (px.inside[k] && dL_ddepth) ? dL_ddepth[pid] : 0.f;
-            dax[k][1] = (px.inside[k] && dL_dalpha_map) ? dL_dalpha_map[pid] : 0.f;
-        }
-        // (-T_final / (1 - alpha)) * bg.dL_dpix = nbg * 1/(1 - alpha)
-        nbg[k] = -Tf * (bg0 * dpx[k][0] + bg1 * dpx[k][1] + bg2 * dpx[k][2]);
-        // kSel: the background term folded into the recurrence -- with
-        // B = T_final bg.dL_dpix / T (so the reference's bg term is -T_new B),
-        // acc_dot + B obeys the same accum recurrence as acc_dot and starts at
-        // bg.dL_dpix: dL_dalpha = T_new (c.dL_dpix - (acc_dot + B)).
-        acc_dot[k] = kSel ? bg0 * dpx[k][0] + bg1 * dpx[k][1] + bg2 * dpx[k][2] : 0.f;
-    }
-    // entries at or past the wave's max n_contrib are skipped by all its pixels
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) wave_last = max(wave_last, (uint32_t)__shfl_xor((int)wave_last, off, 64));
-    // per row group (the lane's k-th pixel): max n_contrib of its 64 pixels;
-    // entries at or past it are skipped by every pixel of the group
-    int group_last[kPPL];
-#pragma unroll
-    for (int k = 0; k < kPPL; k++) {
-        uint32_t g = last[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) g = max(g, (uint32_t)__shfl_xor((int)g, off, 64));
-        group_last[k] = __builtin_amdgcn_readfirstlane((int)g);
-    }
-    // kSel: the smallest n_contrib of each row group's image pixels (pixels
-    // outside the image count as started: their T and dL/dpix are 0, so any
-    // finite alpha leaves their terms 0).  Entries with contributor below it
-    // are taken by every pixel of the group: no per-pixel contributor test.
-    uint32_t min_last = 0xffffffffu;
-    if constexpr (kSel) {
-#pragma unroll
-        for (int k = 0; k < kPPL; k++) {
-            uint32_t g = px.inside[k] ? last[k] : 0xffffffffu;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) g = min(g, (uint32_t)__shfl_xor((int)g, off, 64));
-            min_last = min(min_last, g);
-        }
-        min_last = (uint32_t)__builtin_amdgcn_readfirstlane((int)min_last);
-    }
-    // = max_contrib[tile] for a whole base tile; AMR: no per-tile max_contrib
-    // was recorded for the sub-lattice, the wave max is the block's
-    if constexpr (kDet) {
-        // rows [wave max, min(n, max_contrib)) -- none when max_contrib is this
-        // forward's -- are read by the reduction and visited by no batch: zeros
-        const int mw = min(m, __builtin_amdgcn_readfirstlane((int)wave_last));
-        float* part = grad_accum + (size_t)range.x * kNG;
-        for (int i = mw * kNG + lane; i < m * kNG; i += 64) part[i] = 0.f;
-    }
-    m = min(kAMR ? n : m, __builtin_amdgcn_readfirstlane((int)wave_last));
-    if (m == 0) return;
-    // Row masks: the forward's exact hit codes when it left them (gs_blend.cuh
-    // blend_tile_t: bit r = row group r has a pixel that blended the entry,
-    // i.e. a pixel this backward takes it at), else the geometric cull.
-    // (where the forward stored them: the header word, gs_layout.h hit_codes_of)
-    const uint8_t* const codes = (!kAMR && hdr != nullptr) ? hit_codes_of(point_list, hdr[kHdrHitCodes]) : nullptr;
-    const bool use_codes = codes != nullptr;
-    const float ddelx_dx = (float)(0.5 * W);
-    const float ddely_dy = (float)(0.5 * H);
-    const int comp = lane & 15;
-    // !kSel flush: the accumulator-row entry each output component starts from
-    const int ia = (kAux && comp == kAuxDz) ? kAuxDz : comp < 3 ? comp : comp == 8 ? 3 : comp < 5 ? 4 : comp + 1;
-
-    // Software pipeline over the batches (vector-memory counters retire in
-    // issue order, so issue order decides what each wait covers): the next
-    // batch's point_list ids are loaded while this batch is blended, its
-    // Gaussian records are gathered before this batch's flush atomics are
-    // issued, so neither the id round trip nor the atomics' completion is
-    // waited for at the top of the next batch.
-    // (the hit codes ride with the records: loaded a batch ahead with them, so
-    // the batch's row masks wait for nothing the records did not -- loaded
-    // at the top of the batch, they cost one more memory round trip per
-    // batch, with the next batch's id load behind them in the same counter)
-    uint32_t nid = 0, ncode = 0xfu;
-    float2 nxy = make_float2(0.f, 0.f);
-    float4 nco = make_float4(0.f, 0.f, 0.f, 0.f);
-    float nrgb[3] = {0.f, 0.f, 0.f};
-    float nz = 0.f;  // kAux: the Gaussian's view-space depth
-    if (tid < min(kB, m)) {
-        nid = point_list[range.x + m - 1 - tid];
-        if (use_codes) ncode = codes[range.x + m - 1 - tid];
-        nxy = means2D[nid];
-        nco = conic_opacity[nid];
-        nrgb[0] = colors[3 * nid]; nrgb[1] = colors[3 * nid + 1]; nrgb[2] = colors[3 * nid + 2];
-        if constexpr (kAux) nz = depths[nid];
-        s_id[0][tid] = nid;
-    }
-    // kSel staging reduce: lane (slot = lane / 9, value q = lane % 9) sums the
-    // 16 column partials of value q parked by slot's Gaussian (za rows hold
-    // values swap_sum_slot(r), zb rows 4 + swap_sum_slot(r); swap_sum_slot is
-    // its own inverse) and adds the reference's term into grad_accum.
-    const int st_slot = lane / 9, st_q = lane - 9 * (lane / 9);
-    if constexpr (kSel) {
-        for (int i = lane; i < 3 * kStagePitch + 256; i += 64) s_stage[i] = 0.f;
-    }
-    // writer lane: row r = lane / 16 of za / zb holds values swap_sum_slot(r) /
-    // 4 + swap_sum_slot(r), column c = lane % 16 is element c of that sum.
-    // zb's value v = 4 + swap_sum_slot(r) of (g4, s1, s2, g7) goes to output
-    // q = v except s2 (v = 6) -> q = 8; g6 (q = 6) = dx x (g4's column
-    // partial), formed after the transposition by lanes 0-15 (zb row 0 = g4),
-    // the other lanes' product into their dummy word: no ninth-value DPP tree.
-    const int st_dst = ((lane & 15) >> 2) * kStagePitch + 4 * swap_sum_slot(lane >> 4) + (lane & 3);
-    const int st_dst_b = [&] {
-        const int v = 4 + swap_sum_slot(lane >> 4);
-        return ((lane & 15) >> 2) * kStagePitch + 4 * (v == 6 ? 8 : v) + (lane & 3);
-    }();
-    // (the idle lanes 16-63 store into the 16-word pads of pitch rows 0-2,
-    // which the reduce never reads)
-    const int st_g6 = lane < 16 ? ((lane & 15) >> 2) * kStagePitch + 4 * 6 + (lane & 3)
-                                : ((lane - 16) >> 4) * kStagePitch + 256 + (lane & 15);
-    int par = 0;
-    for (int top = m; top > 0; top -= kB, par ^= 1) {  // entries [top-cnt, top), back to front
-        const int cnt = min(kB, top);
-        __syncthreads();
-        uint32_t gm = 0;
-        bool fastg = false;  // kSel: p2 <= 0 at every pixel of the tile, provably (below)
-        if (tid < cnt) {
-            const float2 xy = nxy;
-            const float4 co = nco;
-            float4 pc = splat_coef(co);
-            // (+ 0: an add where the staged record takes the opacity, so the
-            // compiler forms the b128 store's register tuple here, after the
-            // wait for the gather, instead of with a copy right behind the
-            // gather's issue at the end of the previous batch -- which made
-            // every batch wait a full memory round trip there)
-            pc.w = pc.w + 0.0f;
-            s_a[tid] = make_float4(xy.x, xy.y, nrgb[0], nrgb[1]);
-            s_co[tid] = pc;
-            s_b[tid].x = nrgb[2];
-            if constexpr (kAux) s_b[tid].y = nz;
-            if constexpr (kSel)  // the reference's `power > 0` skip cannot fire (gs_blend.cuh)
-                fastg = splat_form_safe(pc, fabsf(xy.x - (float)ox), fabsf(xy.y - (float)oy)) &&
-                        (!kOpT || (pc.w <= 0.99f && pc.w > 0.0f));
-            gm = use_codes ? ncode : cull ? splat_group_mask(xy, co, (float)ox, (float)oy, (float)pstride) : 0xfu;
-        }
-        const int ntop = top - kB;  // the next batch: entries [ntop - ncnt, ntop)
-        const bool has_next = ntop > 0 && tid < min(kB, ntop);
-        publish_group_masks<1>(gm, s_bal);
-        const uint64_t fast_mask = kSel ? uniform_u64(__ballot(fastg)) : 0ull;
-        if (has_next) {  // (after the masks: nothing below waits on this load until the batch ends)
-            nid = point_list[range.x + ntop - 1 - tid];
-            if (use_codes) ncode = codes[range.x + ntop - 1 - tid];
-        }
-        // every contributor of this batch (<= top - 1) below every row group's
-        // smallest n_contrib: all pixels take its entries
-        const bool bstarted = kSel && (uint32_t)(top - 1) < min_last;
-        uint64_t written = 0;  // !kSel: batch slots whose sum rows were stored
-        int nst = 0;           // kSel: staging slots in use (wave-uniform)
-        uint64_t js = 0;       // kSel: batch slot j of staging slot s in bits [6 s, 6 s + 6)
-        // kSel: the staging reduce finishes the reference's nine terms itself
-        // (lane 9 s + q holds accumulator entry q of slot s's Gaussian; entries
-        // 4 and 5 -- sum t dx, sum t dy -- fetched by two lane shuffles) and
-        // adds them into grad_accum: no accumulator rows in LDS, no per-batch
-        // flush pass, one atomic instruction per 7 Gaussians
-        // kOpT runs of fast entries sum t' = alpha T dL_dalpha / G = o t (below):
-        // the flush takes o out of the mean / conic factors and divides the
-        // opacity sum by it
-        auto stage_reduce = [&](const int nslot, auto kOT) {
-            constexpr bool kOT_ = decltype(kOT)::value;
-            if (nslot == kStageSlots || lane < 9 * nslot) {
-                const float* src = &s_stage[4 * lane];
-                const float4 a = *reinterpret_cast<const float4*>(src);
-                const float4 b = *reinterpret_cast<const float4*>(src + kStagePitch);
-                const float4 c = *reinterpret_cast<const float4*>(src + 2 * kStagePitch);
-                const float4 d = *reinterpret_cast<const float4*>(src + 3 * kStagePitch);
-                const gs_f2 x0 = gs_f2{a.x, a.y} + gs_f2{b.x, b.y}, x1 = gs_f2{a.z, a.w} + gs_f2{b.z, b.w};
-                const gs_f2 x2 = gs_f2{c.x, c.y} + gs_f2{d.x, d.y}, x3 = gs_f2{c.z, c.w} + gs_f2{d.z, d.w};
-                const gs_f2 y = (x0 + x1) + (x2 + x3);
-                const uint32_t jj = (uint32_t)(js >> (6 * st_slot)) & 63u;
-                // lane 9 s + q: output component fq of q (entries 0..2 colours,
-                // 3 = sum t -> opacity (8), 4 = sum t dx -> mean x (3), 5 = sum t
-                // dy -> mean y (4), 6..8 -> conic (5..7)); the flush's formula
-                const float tot = y.x + y.y;
-                const float g4 = __shfl(tot, 9 * st_slot + 4, 64), sy = __shfl(tot, 9 * st_slot + 5, 64);
-                if (lane < 63) {
-                    const int fq = st_q < 3 ? st_q : st_q == 3 ? 8 : st_q - 1;
-                    const float qa = (fq == 3 || fq == 4) ? g4 : tot;
-                    const float4 pc = s_co[jj];
-                    const float o = kOT_ ? 1.0f : pc.w;
-                    const float cx = pc.x * (-1.0f / kHalfLog2e), cy = pc.y * (-1.0f / kLog2e),
-                                cz = pc.z * (-1.0f / kHalfLog2e);
-                    const float ka = fq == 3 ? -o * cx * ddelx_dx
-                                   : fq == 4 ? -o * cy * ddely_dy
-                                   : (fq >= 5 && fq <= 7) ? -0.5f * o
-                                   : (kOT_ && fq == 8) ? 1.0f / pc.w : 1.0f;
-                    const float kb = fq == 3 ? -o * cy * ddelx_dx : fq == 4 ? -o * cz * ddely_dy : 0.0f;
-                    const float v = ka * qa + kb * sy;
-                    if (v != 0.f) atomicAdd(&grad_accum[(size_t)s_id[par][jj] * kGradRow + fq], v);
-                }
-            }
-        };
-        __syncthreads();
-        // first batch slot this wave needs: contributor = top-1-j < wave_last
-        // (readfirstlane: wave_last is uniform after the xor-shuffle max, but the
-        // compiler cannot prove it; without this the bit-scan loop below is
-        // compiled as a divergent VALU loop)
-        const int j0 = __builtin_amdgcn_readfirstlane(max(0, top - (int)wave_last));
-        uint64_t mk[kPPL];
-        uint64_t todo = 0;
-        const uint64_t lo_cut = j0 >= 64 ? 0ull : j0 > 0 ? ~0ull << j0 : ~0ull;
-#pragma unroll
-        for (int k = 0; k < kPPL; k++) {
-            // slots j with contributor = top-1-j < group_last[k], i.e. j >= top - group_last[k]
-            const int jk = top - group_last[k];
-            const uint64_t gcut = jk <= 0 ? ~0ull : (jk >= 64 ? 0ull : ~0ull << jk);
-            mk[k] = uniform_u64(s_bal[k]) & lo_cut & gcut;
-            todo |= mk[k];
-        }
-        // One Gaussian (batch slot j, record staged in LDS) against the wave's
-        // pixels.  (Reading the next set bit's record ahead, in two register
-        // sets used in turn, measured no faster: the 4 waves per SIMD already
-        // hide the LDS latency.)
-        auto visit = [&](const int j, const float2 xy, const float4 pc, const float4 cf, auto kFastT, auto kStartedT,
-                         auto kSlotT) {
-            constexpr bool kFast = decltype(kFastT)::value, kStarted = decltype(kStartedT)::value;
-            constexpr int kSlot = decltype(kSlotT)::value;  // kSel: this entry's staging slot
-            const uint32_t contributor = (uint32_t)(top - 1 - j);
-            const float dx = xy.x - px.x;
-            const float pa = (pc.x * dx) * dx, pb = pc.y * dx;  // the lane's pixels share x
-            // Per pixel with t = G dL_dalpha the reference adds (backward.cu:
-            // 518-545) dL_dopacity += t; dL_dmean2D += -o t (C d) * (W/2, H/2);
-            // dL_dconic += -o/2 t (dx^2, dx dy, dy^2).  A lane's pixels share dx,
-            // so it sums s0 = sum t, s1 = sum t dy, s2 = sum t dy^2 and forms
-            // the six moments (s0, dx s0, s1, dx^2 s0, dx s1, s2) once; the flush
-            // applies o, the conic and the constants.
-            // (-0: x + -0 == x for every x, so the first visited row group's
-            // fma(a, b, -0) / -0 + t fold to a plain v_mul / move instead of a
-            // 3-operand fma with an inline 0)
-            float c0 = -0.f, c1 = -0.f, c2 = -0.f, s0 = -0.f, s1 = -0.f, s2 = -0.f;
-            float c3 = 0.f;  // kAux: sum alpha T dL_ddepth (cf.w = z)
-            bool any = false;
-            if constexpr (kSel) {
-                // The select form: a rejected pixel takes alpha = G = 0, i.e.
-                // rinv = 1 (T unchanged), dchannel = t = 0 and acc_dot += 0 --
-                // the same bits as the predicate form for every accepted pixel,
-                // no exec-mask bookkeeping: a visited Gaussian is always summed
-                // (with the forward's hit codes a visited row group has a pixel
-                // that blended; under the geometric cull an all-rejected visit
-                // sums zeros, which the flush skips).  The selects take an
-                // SGPR-pair mask (gs_sel2_zero_v) and only the compares the
-                // entry needs: alpha >= 1/255 always; contributor < n_contrib
-                // unless the batch is started for every pixel; power > 0 only
-                // for Gaussians not provably negative definite (fast_mask).
-#pragma unroll
-                for (int k = 0; k < kPPL; k++) {
-                    if (!((mk[k] >> j) & 1ull)) continue;  // wave-uniform
-                    const float dy = xy.y - (py0 + (float)(4 * k * (int)pstride));
-                    const float p2 = splat_p2(pa, pb, dy, pc);
-                    const float Gr = splat_exp(p2);
-                    const float ar = fminf(0.99f, pc.w * Gr);
-                    uint64_t msk = __builtin_amdgcn_fcmpf(ar, 1.0f / 255.0f, kFcmpUGE);
-                    if (!kFast || !kStarted) msk &= __builtin_amdgcn_uicmp(contributor, last[k], kIcmpULT);
-                    if (!kFast) msk &= __builtin_amdgcn_fcmpf(p2, 0.0f, kFcmpULE);
-                    // kOpT and a fast entry (o <= 0.99, p2 <= 0: alpha = o G
-                    // unclamped, bit for bit the rounded product): t' = o t =
-                    // alpha T (c - acc) = dchannel_dcolor diff -- no G select,
-                    // one product fewer; the flush divides o back out
-                    constexpr bool kOT = kOpT && kFast;
-                    float G, alpha;
-                    if constexpr (kOT) alpha = gs_sel_zero_v(msk, ar);
-                    else gs_sel2_zero_v(msk, Gr, ar, G, alpha);
-                    const float rinv = __builtin_amdgcn_rcpf(1.f - alpha);
-                    T[k] = T[k] * rinv;
-                    const float dchannel_dcolor = alpha * T[k];
-                    // (c - accum_rec - B) . dL_dpix as one fma chain
-                    const float diff = __builtin_fmaf(cf.z, dpx[k][2],
-                                                      __builtin_fmaf(cf.y, dpx[k][1],
-                                                                     __builtin_fmaf(cf.x, dpx[k][0], -acc_dot[k])));
-                    acc_dot[k] = __builtin_fmaf(alpha, diff, acc_dot[k]);
-                    c0 = __builtin_fmaf(dchannel_dcolor, dpx[k][0], c0);
-                    c1 = __builtin_fmaf(dchannel_dcolor, dpx[k][1], c1);
-                    c2 = __builtin_fmaf(dchannel_dcolor, dpx[k][2], c2);
-                    const float t = kOT ? dchannel_dcolor * diff : G * (diff * T[k]);
-                    const float tdy = t * dy;
-                    s0 += t;
-                    s1 += tdy;
-                    s2 = __builtin_fmaf(tdy, dy, s2);
-                }
-                any = true;
-            } else {
-#pragma unroll
-                for (int k = 0; k < kPPL; k++) {
-                    if (!((mk[k] >> j) & 1ull)) continue;  // wave-uniform: culled for this row group
-                    const float dy = xy.y - (py0 + (float)(4 * k * (int)pstride));
-                    const float p2 = splat_p2(pa, pb, dy, pc);  // the forward's bits
-                    const float G = splat_exp(p2);
-                    const float alpha = fminf(0.99f, pc.w * G);
-                    // The reference's three per-pixel `continue`s (backward.cu:466-482)
-                    // as one predicate: only wave-uniform branches save SIMD time, and
-                    // nested ones make the compiler re-zero g[] on every skip path.
-                    // (contributor >= last also covers pixels outside the image.)
-                    const bool ok = contributor < last[k] && !(p2 > 0.0f) && !(alpha < 1.0f / 255.0f);
-                    if (!ok) continue;
-                    any = true;
-                    const float rinv = __builtin_amdgcn_rcpf(1.f - alpha);
-                    T[k] = T[k] * rinv;
-                    const float dchannel_dcolor = alpha * T[k];
-                    // sum_ch (c - accum_rec) dL_dpix, with accum_rec . dL_dpix
-                    // advanced by the reference's recurrence (backward.cu:500-507)
-                    float c_dot = cf.x * dpx[k][0] + cf.y * dpx[k][1] + cf.z * dpx[k][2];
-                    if constexpr (kAux) {  // the channels (z, 1)
-                        c_dot += cf.w * dax[k][0] + dax[k][1];
-                        c3 = __builtin_fmaf(dchannel_dcolor, dax[k][0], c3);
-                    }
-                    // The reference advances accum_rec at the NEXT contributor from the
-                    // stored (last_alpha, last_color); advancing it here with the same
-                    // operands gives the same bits and needs no per-pixel "last" state.
-                    const float diff = c_dot - acc_dot[k];
-                    const float dL_dalpha = diff * T[k] + nbg[k] * rinv;
-                    acc_dot[k] = __builtin_fmaf(alpha, diff, acc_dot[k]);
-                    c0 = __builtin_fmaf(dchannel_dcolor, dpx[k][0], c0);
-                    c1 = __builtin_fmaf(dchannel_dcolor, dpx[k][1], c1);
-                    c2 = __builtin_fmaf(dchannel_dcolor, dpx[k][2], c2);
-                    const float t = G * dL_dalpha;
-                    const float tdy = t * dy;
-                    s0 += t;
-                    s1 += tdy;
-                    s2 = __builtin_fmaf(tdy, dy, s2);
-                }
-            }
-            float g[kNG];
-            g[0] = c0;
-            g[1] = c1;
-            g[2] = c2;
-            g[3] = s0;
-            g[4] = dx * s0;
-            g[5] = s1;
-            g[6] = kSel ? s2 : dx * g[4];
-            g[7] = dx * s1;
-            g[8] = s2;
-            if constexpr (kSel) {
-                // s2 rides in the 8-value transposition (g6 = dx^2 s0 leaves it;
-                // g6's column partials are dx x g4's, formed after it)
-                float za, zb;
-                swap_rows8_pk_t<false>(g, za, zb);
-                const float w6 = dx * zb;
-                s_stage[st_dst + 36 * kSlot] = za;
-                s_stage[st_dst_b + 36 * kSlot] = zb;
-                s_stage[st_g6 + (lane < 16 ? 36 * kSlot : 0)] = w6;
-                js |= (uint64_t)j << (6 * kSlot);
-            } else if (__ballot(any) != 0ull) {  // wave-uniform
-                // full sums by transposition: 2 values per row leader + g8 in lane 63
-                float za, zb;
-                swap_sum9(g, za, zb);
-                if constexpr (kAux) {  // the tenth sum: the plain DPP tree, total in lane 63
-                    c3 = dpp_add<0x111, 0xf, true>(c3);   // row_shr:1
-                    c3 = dpp_add<0x112, 0xf, true>(c3);   // row_shr:2
-                    c3 = dpp_add<0x114, 0xf, true>(c3);   // row_shr:4
-                    c3 = dpp_add<0x118, 0xf, true>(c3);   // row_shr:8
-                    c3 = dpp_add<0x142, 0xa, false>(c3);  // row_bcast:15
-                    c3 = dpp_add<0x143, 0xc, false>(c3);  // row_bcast:31
-                }
-                if ((lane & 15) == 15) {
-                    float* row = &s_acc[j * kRow];
-                    const int q = swap_sum_slot(lane >> 4);
-                    row[q] = za;
-                    row[4 + q] = zb;
-                    if (lane == 63) {
-                        row[8] = g[8];
-                        if constexpr (kAux) row[kAuxDz] = c3;
-                    }
-                }
-                written |= 1ull << j;
-            }
-        };
-        using T1 = std::integral_constant<bool, true>;
-        using T0 = std::integral_constant<bool, false>;
-        using S0 = std::integral_constant<int, 0>;
-        if constexpr (kSel) {
-            // one copy of the loop per (all-safe, started) batch case, chosen
-            // once per batch -- per-entry branches between the visit variants
-            // made the register allocator shuffle the loop-carried pixel state
-            // (8 v_mov per entry) at every join.  Rounds of 7 entries, one
-            // unrolled copy of the visit per staging slot (slot offsets as
-            // immediates, no per-entry slot counter or address VALU, the
-            // visited bit cleared by one s_andn2)
-            auto run = [&](auto kFastT, auto kStartedT) {
-                auto one = [&](auto kSlotT) {
-                    if (!todo) return;  // wave-uniform
-                    const int j = __builtin_ctzll(todo);
-                    todo &= ~(1ull << j);
-                    const float4 a4 = s_a[j];
-                    const float2 xy = make_float2(a4.x, a4.y);
-                    const float4 pc = s_co[j], cf = make_float4(a4.z, a4.w, s_b[j].x, 0.f);
-                    visit(j, xy, pc, cf, kFastT, kStartedT, kSlotT);
-                    nst = decltype(kSlotT)::value + 1;
-                };
-                while (todo) {
-                    one(S0{});
-                    one(std::integral_constant<int, 1>{});
-                    one(std::integral_constant<int, 2>{});
-                    one(std::integral_constant<int, 3>{});
-                    one(std::integral_constant<int, 4>{});
-                    one(std::integral_constant<int, 5>{});
-                    one(std::integral_constant<int, 6>{});
-                    if (nst == kStageSlots) {
-                        stage_reduce(kStageSlots, std::integral_constant<bool, kOpT && decltype(kFastT)::value>{});
-                        nst = 0;
-                        js = 0ull;
-                    }
-                }
-                if (nst) stage_reduce(nst, std::integral_constant<bool, kOpT && decltype(kFastT)::value>{});
-                nst = 0;
-            };
-            // every entry this wave visits has a provably negative-definite form
-            const bool bsafe = (todo & ~fast_mask) == 0ull;
-            if (bsafe && bstarted) run(T1{}, T1{});
-            else if (bsafe) run(T1{}, T0{});
-            else run(T0{}, T0{});
-        } else {
-            while (todo) {
-                const int j = __builtin_ctzll(todo);
-                todo &= todo - 1;
-                const float4 a4 = s_a[j];
-                const float2 xy = make_float2(a4.x, a4.y);
-                const float4 pc = s_co[j], cf = make_float4(a4.z, a4.w, s_b[j].x, kAux ? s_b[j].y : 0.f);
-                visit(j, xy, pc, cf, T0{}, T0{}, S0{});
-            }
-        }
-        __syncthreads();
-        if (has_next) {  // gathers for the next batch, ahead of the flush atomics
-            s_id[par ^ 1][tid] = nid;
-            nxy = means2D[nid];
-            nco = conic_opacity[nid];
-            nrgb[0] = colors[3 * nid]; nrgb[1] = colors[3 * nid + 1]; nrgb[2] = colors[3 * nid + 2];
-            if constexpr (kAux) nz = depths[nid];
-        }
-        if constexpr (!kSel) {
-            // Flush: 16 lanes per Gaussian row, 4 rows per wave instruction
-            // (one 64-B memory-side atomic request per (tile, Gaussian)).  (A full
-            // unroll lets the scheduler hoist all 64 LDS reads: 163 VGPRs.)
-#pragma unroll 4
-            for (int i = 0; i < kB / 4; i++) {
-                const int r = (tid >> 4) + 4 * i;
-                const bool wr = (written >> (r & 63)) & 1ull;
-                if constexpr (kDet) {
-                    // a row no pixel took stores zeros: every row the reduction
-                    // reads is written by this call
-                    if (r < cnt && comp < kNG && !wr)
-                        grad_accum[(size_t)(range.x + (uint32_t)(top - 1 - r)) * kNG + comp] = 0.f;
-                }
-                const bool live = r < cnt && comp < kRow && wr;
-                if (live) {
-                    // row sums (c0, c1, c2, s0, sx, sy, sxx, sxy, syy) -> the
-                    // reference's nine terms: v = ka * row[ia] + kb * sy, with o and
-                    // the conic from the staged log2(e)-scaled record
-                    const float* row0 = &s_acc[r * kRow];
-                    const float qa = row0[ia], qb = row0[5];
-                    const float4 pc = s_co[r];
-                    const float o = pc.w;
-                    const float cx = pc.x * (-1.0f / kHalfLog2e), cy = pc.y * (-1.0f / kLog2e),
-                                cz = pc.z * (-1.0f / kHalfLog2e);
-                    const float ka = comp == 3 ? -o * cx * ddelx_dx
-                                   : comp == 4 ? -o * cy * ddely_dy
-                                   : (comp >= 5 && comp <= 7) ? -0.5f * o : 1.0f;
-                    const float kb = comp == 3 ? -o * cy * ddelx_dx : comp == 4 ? -o * cz * ddely_dy : 0.0f;
-                    const float v = ka * qa + kb * qb;
-                    if constexpr (kDet) grad_accum[(size_t)(range.x + (uint32_t)(top - 1 - r)) * kNG + comp] = v;
-                    else if (v != 0.f) atomicAdd(&grad_accum[(size_t)s_id[par][r] * kGradRow + comp], v);
-                }
-            }
-        }
-    }
-}
-
-extern int g_cull;  // render.hip
 // Backward variants (set_tuning("bwd_variant")).  Default: round 4's variant
 // 11 -- the select form with SGPR-pair masks, per-batch compare sets, staged
 // sums and the flush fused into the staging reduce: render_bwd 0.3707
@@ -658,13 +46,13 @@ extern int g_cull;  // render.hip
 // 0.3403 (unrolled slots) -> 0.3139 ms (fused flush) at config 2, 0.2887 ->
 // 0.2433 at config 4 (profiles/r04b_ab_bwd*.log, r04e_ab_bwd*.log,
 // r04l_ab_bwd*_m.log) -- plus, since round 5, the opacity-scaled sums
-// (kOpT): in batches of provably negative-definite entries with o <= 0.99
+// (always on): in batches of provably negative-definite entries with o <= 0.99
 // (alpha = o G unclamped, bit for bit the rounded product) the visit sums t'
 // = alpha T (c - acc) . dL_dpix = o t, which needs no G select and one
 // product less, and the flush takes o out of the mean / conic factors and
 // divides the opacity sum by it (0.3116 -> 0.3063 ms at config 2, 0.2385 ->
 // 0.2348 at config 4, profiles/r05d_ab_bwd_opt*.log).  Fallback (0): the
-// predicate form with full sums in LDS rows (also the AMR backward's form).
+// predicate form with full sums in LDS rows (render_bwd_rows_kernel).
 // Measured and removed (logs in profiles/): 2 waves x 2 px and 4 x 1
 // geometries, half-wave DPP-tree sums, a 5-wave occupancy cap (spills), the
 // un-fused staged forms, the heavy-tile split (r01h / DESIGN.md §8e), an
@@ -674,29 +62,32 @@ constexpr int kDefaultBwdVariant = 2;
 int g_bwd_variant = kDefaultBwdVariant;
 void set_backward_variant(int v) { g_bwd_variant = v == 0 ? 0 : kDefaultBwdVariant; }
 
+// The kernel arguments every blend backward launch shares (member order of BlendBwdParams; the extras zero).
+// Tiles heaviest first: the forward render filled this image buffer's 256 work buckets (the kernels fall back to
+// the identity order otherwise); the forward's hit codes are found through the header (gs_layout.h hit_codes_of).
+static BlendBwdParams blend_bwd_params(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
+                                       const float* colors, const float* bg, const float* dL_dpix) {
+    return BlendBwdParams{W, H, img.ranges, img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
+                          reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
+                          dL_dpix, bg, g.grad_accum, g_cull, (W + 15) / 16, img.bucket_count, img.bucket_list, g.hdr};
+}
+
 void launch_render_backward(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
-                            const float* colors, const float* bg, const float* dL_dpix, hipStream_t s, int K) {
-    (void)K;  // (the forward's hit codes are found through the header, gs_layout.h hit_codes_of)
+                            const float* colors, const float* bg, const float* dL_dpix, hipStream_t s) {
     const int gx = (W + 15) / 16, gy = (H + 15) / 16;
     if (gx == 0 || gy == 0) return;
-    // tiles heaviest first: the forward render filled this image buffer's 256
-    // work buckets (the kernel falls back to the identity order otherwise)
+    const BlendBwdParams p = blend_bwd_params(W, H, img, b, g, colors, bg, dL_dpix);
     // (the profiler's stage events, if any, ride on the dispatch itself)
     const DispatchEvents ev = take_dispatch_events();
-#define GS_BWD_LAUNCH(...)                                                                                         \
-    hipExtLaunchKernelGGL((render_bwd_kernel<__VA_ARGS__>), dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0, W, H,     \
-                       img.ranges, img.max_contrib,                                                                \
-                       b.point_list, reinterpret_cast<const float2*>(g.means2D),                                   \
-                       reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,    \
-                       dL_dpix, bg, g.grad_accum, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list,       \
-                       g.hdr, nullptr, nullptr, nullptr)
-    if (g_bwd_variant == 0) GS_BWD_LAUNCH(false);
-    else GS_BWD_LAUNCH(true, false, true);
-#undef GS_BWD_LAUNCH
+    if (g_bwd_variant == 0)
+        hipExtLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kBase>, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop,
+                              0, p);
+    else
+        hipExtLaunchKernelGGL(render_bwd_kernel, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0, p);
 }
 
 // The deterministic backward's second pass: grad_accum[p][0..8] of every
-// visible Gaussian = the sum of its partial rows (render_bwd_kernel kDet)
+// visible Gaussian = the sum of its partial rows (render_bwd_rows_kernel kDet)
 // over the tiles of its rectangle in ascending tile index, accumulated in
 // float64 and rounded to float32 once, stored with a plain store -- the same
 // bits whatever order the blend's workgroups ran in.
@@ -791,11 +182,9 @@ void launch_render_backward_deterministic(int W, int H, int P, int R, const Imag
     if (gx == 0 || gy == 0 || P <= 0 || R <= 0) return;
     // the partials array in grad_accum's place (kDet); the forward's work
     // buckets still order the launch, heaviest tiles first
-    hipLaunchKernelGGL((render_bwd_kernel<false, false, false, true>), dim3(gx * gy), dim3(64), 0, s, W, H, img.ranges,
-                       img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
-                       reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
-                       dL_dpix, bg, partials, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr,
-                       nullptr, nullptr, nullptr);
+    BlendBwdParams p = blend_bwd_params(W, H, img, b, g, colors, bg, dL_dpix);
+    p.grad_accum = partials;
+    hipLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kDet>, dim3(gx * gy), dim3(64), 0, s, p);
     const unsigned groups = ((unsigned)P + 15u) / 16u;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(groups), dim3(256), 0, s, P, (uint32_t)R, (uint32_t)gx,
                        (uint32_t)gy, radii, reinterpret_cast<const float2*>(g.means2D), g.depths, g.tiles_touched,
@@ -803,7 +192,7 @@ void launch_render_backward_deterministic(int W, int H, int P, int R, const Imag
 }
 
 // The blend backward with the depth and alpha maps' cotangents
-// (gs_rasterizer_backward_aux): render_bwd_kernel kAux, five channels in one
+// (gs_rasterizer_backward_aux): render_bwd_rows_kernel kAux, five channels in one
 // walk of the tile lists, ten sums per Gaussian into g.grad_accum.
 void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                                 const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
@@ -811,12 +200,12 @@ void launch_render_backward_aux(int W, int H, const ImageView& img, const Binnin
     const int gx = (W + 15) / 16, gy = (H + 15) / 16;
     if (gx == 0 || gy == 0) return;
     const DispatchEvents ev = take_dispatch_events();
-    hipExtLaunchKernelGGL((render_bwd_kernel<false, false, false, false, true>), dim3(gx * gy), dim3(64), 0, s,
-                          ev.start, ev.stop, 0, W, H, img.ranges, img.max_contrib, b.point_list,
-                          reinterpret_cast<const float2*>(g.means2D),
-                          reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
-                          dL_dpix, bg, g.grad_accum, g_cull, gx, 0, nullptr, img.bucket_count, img.bucket_list, g.hdr,
-                          g.depths, dL_ddepth, dL_dalpha);
+    BlendBwdParams p = blend_bwd_params(W, H, img, b, g, colors, bg, dL_dpix);
+    p.depths = g.depths;
+    p.dL_ddepth = dL_ddepth;
+    p.dL_dalpha = dL_dalpha;
+    hipExtLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kAux>, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0,
+                          p);
 }
 
 // The depth map's direct term on the means: z = V[2] x + V[6] y + V[10] z +
@@ -851,11 +240,11 @@ void launch_amr_render_backward(int W, int H, int mode, const ImageView& img, co
                                 hipStream_t s) {
     const int tgx = (W + 31) / 32, tgy = (H + 31) / 32;
     if (tgx == 0 || tgy == 0 || mode == 0) return;
-    hipLaunchKernelGGL((render_bwd_kernel<false, true>), dim3(4 * tgx * tgy), dim3(64), 0, s, W, H, img.ranges,
-                       img.max_contrib, b.point_list, reinterpret_cast<const float2*>(g.means2D),
-                       reinterpret_cast<const float4*>(g.conic_opacity), colors, img.accum_alpha, img.n_contrib,
-                       dL_dpix, bg, g.grad_accum, g_cull, tgx, mode, img.levels, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
+    BlendBwdParams p = blend_bwd_params(W, H, img, b, g, colors, bg, dL_dpix);
+    p.amr_mode = mode;
+    p.levels = img.levels;
+    p.gx = tgx;
+    hipLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kAmr>, dim3(4 * tgx * tgy), dim3(64), 0, s, p);
 }
 
 // (the per-Gaussian backward math: gs_bwd_math.cuh)

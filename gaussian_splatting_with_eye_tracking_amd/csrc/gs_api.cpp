@@ -784,7 +784,7 @@ void blend_backward(const DetScratch& det, int width, int height, int P, int R, 
         zero_accum_unless_clean(g, P, s);
         if (R > 0 && P > 0) {
             StageTimer _t(kRenderBwd, s, true);
-            launch_render_backward(width, height, img, b, g, colors, background, dL_dpix, s, R);
+            launch_render_backward(width, height, img, b, g, colors, background, dL_dpix, s);
         }
         return;
     }

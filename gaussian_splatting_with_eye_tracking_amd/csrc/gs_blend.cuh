@@ -267,6 +267,18 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// The wave's max / min of v, in every lane (xor-shuffle butterfly).
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, kWave));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, kWave));
+    return v;
+}
+
 // Per batch: s_bal[c * 4 + r] = 64-bit mask over batch slots 64c..64c+63 of
 // the Gaussians meeting row group r.  Called by every thread after it has
 // computed the mask of its own slot (0 for empty slots).

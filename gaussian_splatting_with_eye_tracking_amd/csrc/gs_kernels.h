@@ -115,7 +115,7 @@ void launch_render_forward_aux(int W, int H, const ImageView& img, const Binning
                                float* out_depth, float* out_alpha, hipStream_t s);
 // Their backward: the blend backward over five channels (colour, z, 1) into
 // g.grad_accum -- floats 0..8 the totals of the nine sums, float kAuxDz
-// dL/dz (backward.hip render_bwd_kernel kAux).  Any cotangent may be null.
+// dL/dz (gs_blend_bwd.cuh render_bwd_rows_kernel kAux).  Any cotangent may be null.
 void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                                 const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
                                 const float* dL_dalpha, hipStream_t s);
@@ -131,7 +131,7 @@ void set_cull(int v);  // row-group cull in the blend kernels (default on)
 void set_ritnet_mfma(int v);
 // Blend backward (base/cr/backward.cu:399-557) into g.grad_accum.
 void launch_render_backward(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
-                            const float* colors, const float* bg, const float* dL_dpix, hipStream_t s, int K);
+                            const float* colors, const float* bg, const float* dL_dpix, hipStream_t s);
 // The same in a fixed summation order (gs_rasterizer_backward_deterministic):
 // the blend stores one row of kDetRow floats per sorted instance into
 // `partials` ([R][kDetRow], plain stores, no atomics), then a reduction sums

@@ -21,12 +21,6 @@
 
 namespace gsamd {
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, kWave));
-    return v;
-}
-
 template <int kPPL>
 __device__ __forceinline__ void write_pixels(const PixelSetT<kPPL>& px, const BlendStateT<kPPL>& st, int W, int H,
                                              float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,

@@ -46,6 +46,7 @@ from collections import defaultdict
 # substring of the kernel name -> stage (first match wins; more specific first)
 STAGES = [
     ("render_bwd_kernel", "render_bwd"),
+    ("render_bwd_rows_kernel", "render_bwd"),
     ("render_fwd_kernel", "render"),
     ("duplicate_lds_kernel", "duplicate"),
     ("band_stage_kernel", "duplicate"),
