@@ -13,7 +13,13 @@ the reference's own optimiser machinery restated in oracle/train_oracle.py
   put in the identical state and both run train.py:108-125 at iterations that
   densify, reset opacity and step; structure (P, masks) must match exactly,
   values to Adam's tolerance.
+* the fused iteration against the autograd one, on models of every SH size
+  at sizes that are no multiple of 4, accumulating over two views after the
+  deferred zeroing, and after densification changed P.
 * a short training run fits a target image (loss falls, P changes, no NaN).
+
+The kernels themselves are held element by element in
+test_gpu_train_kernels.py.
 """
 import math
 
@@ -171,23 +177,10 @@ def test_post_backward_lockstep_with_reference(iteration, fused):
     assert_close_state(m, o)
 
 
-@pytest.mark.parametrize("active_sh", [0, 3])
-def test_fused_path_matches_autograd_path(active_sh):
-    """render_and_backward (activation kernels, fused loss gradient straight
-    into the rasterizer backward, no autograd) against torch activations +
-    the drop-in autograd rasterizer + l1_ssim_loss + loss.backward(): image
-    and radii identical, raw-parameter gradients within 1e-5 relative."""
+def _assert_fused_matches_autograd(out, active_sh):
+    """The bars of test_fused_path_matches_autograd_path on
+    [(model, pkg, terms) fused, (model, pkg, terms) autograd]."""
     T = _T()
-    sc, cam, s = _render_case(P=5000, W=160, H=120, seed=9)
-    raw = raw_from_scene(sc)
-    raw["rotation"] = raw["rotation"] * torch.linspace(0.5, 2.0, 5000, device="cuda")[:, None]  # unnormalised
-    gt = torch.rand(3, 120, 160, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
-    out = []
-    for fused in (True, False):
-        m = T.FlatGaussianModel(raw, 3, spatial_lr_scale=5.0)
-        m.active_sh_degree = active_sh
-        pkg, terms = T.forward_backward(m, 1, s, gt, fused=fused)
-        out.append((m, pkg, terms))
     (mf, pf, tf), (ma, pa, ta) = out
     torch.testing.assert_close(pf["render"], pa["render"].detach(), rtol=0, atol=1e-6)
     assert torch.equal(pf["radii"], pa["radii"])
@@ -195,10 +188,162 @@ def test_fused_path_matches_autograd_path(active_sh):
     torch.testing.assert_close(pf["viewspace_grad"], pa["viewspace_grad"], rtol=1e-5, atol=1e-9)
     for g in T.GROUPS:
         a, b = mf.group_view(mf.grads, g), ma.group_view(ma.grads, g)
+        assert a.shape == b.shape and bool(torch.isfinite(a).all()), g
         rel = float((a - b).norm() / b.norm().clamp_min(1e-30))
         assert rel < 1e-5, (g, rel)
-        if g == "f_rest" and active_sh == 0:
+        if g == "f_rest" and active_sh == 0 and a.numel():
             assert float(a.abs().max()) == 0.0
+
+
+def _truncate_sh(raw, max_sh_degree):
+    """The raw groups of a model with fewer SH bands (f_rest [P, M - 1, 3], empty at degree 0)."""
+    raw = dict(raw)
+    raw["f_rest"] = raw["f_rest"][:, :(max_sh_degree + 1) ** 2 - 1].contiguous()
+    return raw
+
+
+def _fused_vs_autograd(P, max_sh_degree, active_sh):
+    T = _T()
+    sc, cam, s = _render_case(P=P, W=160, H=120, seed=9)
+    raw = _truncate_sh(raw_from_scene(sc), max_sh_degree)
+    raw["rotation"] = raw["rotation"] * torch.linspace(0.5, 2.0, P, device="cuda")[:, None]  # unnormalised
+    gt = torch.rand(3, 120, 160, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
+    out = []
+    for fused in (True, False):
+        m = T.FlatGaussianModel(raw, max_sh_degree, spatial_lr_scale=5.0)
+        m.active_sh_degree = active_sh
+        pkg, terms = T.forward_backward(m, 1, s, gt, fused=fused)
+        out.append((m, pkg, terms))
+    _assert_fused_matches_autograd(out, active_sh)
+    return out
+
+
+@pytest.mark.parametrize("active_sh", [0, 3])
+def test_fused_path_matches_autograd_path(active_sh):
+    """render_and_backward (activation kernels, fused loss gradient straight
+    into the rasterizer backward, no autograd) against torch activations +
+    the drop-in autograd rasterizer + l1_ssim_loss + loss.backward(): image
+    and radii identical, raw-parameter gradients within 1e-5 relative."""
+    _fused_vs_autograd(5000, 3, active_sh)
+
+
+@pytest.mark.parametrize("P,max_sh_degree,active_sh", [(4999, 3, 3), (4998, 1, 1), (4997, 0, 0)])
+def test_fused_path_matches_autograd_path_models(P, max_sh_degree, active_sh):
+    """The same comparison on models of every SH size the trainer builds
+    (M = 16, 4, 1; at M = 1 features_rest is empty) and at sizes that are no
+    multiple of 4: the rotation segment of the flat buffers then starts at a
+    float offset that is no multiple of 4, where the activation kernels'
+    float4 accesses are not 16-byte aligned."""
+    out = _fused_vs_autograd(P, max_sh_degree, active_sh)
+    mf = out[0][0]
+    assert mf.group_view(mf.params, "rotation").data_ptr() % 16 != 0
+    assert mf.group_view(mf.grads, "rotation").data_ptr() % 16 != 0
+    assert mf.param["f_rest"].shape == (P, (max_sh_degree + 1) ** 2 - 1, 3)
+
+
+def test_fused_accumulate_sums_two_views():
+    """render_and_backward(accumulate=True) over two views after the deferred
+    zeroing (zero_grad(memset=False)): the stale buffer -- NaN here -- is
+    zeroed exactly once, by the first accumulating call, and every group ends
+    as the sum of the two views' separate gradients (1e-5 relative, the
+    file's bar).  And a plain call after the deferred zeroing overwrites
+    every gradient: the view's own again, exact zeros in the rows of the
+    Gaussians it culled."""
+    T = _T()
+    P = 4999
+    sc, cam, s_a = _render_case(P=P, W=160, H=120, seed=11)
+    cam_b = G.S.make_camera(160, 120, R=G._rot("y", 14.0) @ G._rot("x", -6.0), T=np.array([0.35, -0.1, 0.4]))
+    s_b = G.torch_settings(cam_b)
+    raw = raw_from_scene(sc)
+    gen = torch.Generator("cuda").manual_seed(3)
+    gts = [torch.rand(3, 120, 160, device="cuda", generator=gen) for _ in range(2)]
+
+    def model():
+        m = T.FlatGaussianModel(raw, 3, spatial_lr_scale=5.0)
+        m.active_sh_degree = 3
+        return m
+
+    single = []
+    for s, gt in zip((s_a, s_b), gts):
+        m = model()
+        pkg, _ = m.render_and_backward(s, gt, m.opt.lambda_dssim)
+        single.append((m.grads.clone(), pkg["radii"].clone()))
+    (g_a, radii_a), (g_b, radii_b) = single
+    assert bool((radii_a == 0).any()) and bool((radii_b == 0).any())
+    assert bool(((radii_a == 0) != (radii_b == 0)).any())  # the views do not cull the same Gaussians
+    assert float((g_a - g_b).norm()) > 0.1 * float(g_a.norm())
+
+    m = model()
+    assert m.group_view(m.grads, "rotation").data_ptr() % 16 != 0
+    m.grads.fill_(float("nan"))
+    m.zero_grad(memset=False)
+    assert bool(torch.isnan(m.grads).all())  # deferred: nothing zeroed yet
+    m.render_and_backward(s_a, gts[0], m.opt.lambda_dssim, accumulate=True)
+    m.render_and_backward(s_b, gts[1], m.opt.lambda_dssim, accumulate=True)
+    want = g_a + g_b
+    for g in T.GROUPS:
+        a, b = m.group_view(m.grads, g), m.group_view(want, g)
+        rel = float((a - b).norm() / b.norm().clamp_min(1e-30))
+        assert rel < 1e-5, (g, rel)
+        one = float((a - m.group_view(g_a, g)).norm() / b.norm().clamp_min(1e-30))
+        assert one > 1e-3, (g, one)  # the second view did add to it
+
+    m.grads.fill_(float("nan"))
+    m.zero_grad(memset=False)
+    pkg, _ = m.render_and_backward(s_a, gts[0], m.opt.lambda_dssim)
+    assert torch.equal(pkg["radii"], radii_a)
+    culled = pkg["radii"] == 0
+    for g in T.GROUPS:
+        a, b = m.group_view(m.grads, g), m.group_view(g_a, g)
+        rel = float((a - b).norm() / b.norm().clamp_min(1e-30))
+        assert rel < 1e-5, (g, rel)
+        assert bool((a[culled] == 0).all()), g
+
+
+def _densified_model(seed, fused=True):
+    """A model mid-training taken through forward_backward + post_backward at
+    iteration 3000 (densify, prune, opacity reset, Adam, deferred zeroing)."""
+    T = _T()
+    iteration = 3000
+    sc, cam, s = _render_case(P=3000, W=160, H=120, seed=seed)
+    m = T.FlatGaussianModel(raw_from_scene(sc), 3, spatial_lr_scale=5.0)
+    m.active_sh_degree = 3
+    gen = torch.Generator().manual_seed(seed)
+    for g in T.GROUPS:
+        m.group_view(m.exp_avg, g).copy_(torch.randn(m.param[g].shape, generator=gen) * 1e-4)
+        m.group_view(m.exp_avg_sq, g).copy_(torch.rand(m.param[g].shape, generator=gen) * 1e-8)
+        m.steps[g] = iteration - 1
+    m.xyz_gradient_accum.copy_(torch.rand(m.P, 1, generator=gen) * 0.002)
+    m.denom.copy_(torch.randint(0, 8, (m.P, 1), generator=gen).float())
+    gt = torch.rand(3, 120, 160, generator=gen).cuda()
+    pkg, _ = T.forward_backward(m, iteration, s, gt, fused=fused)
+    torch.manual_seed(seed)
+    T.post_backward(m, iteration, pkg, scene_extent=5.0, fused=fused)
+    return m, s, gt
+
+
+DENSIFY_SEED = 4  # 3000 -> 5263 Gaussians (seeds 0 and 1 give 5312 and 5260, multiples of 4)
+
+
+def test_fused_step_after_densification():
+    """After densify_and_prune rebuilt the flat buffers at a size that is no
+    multiple of 4 (and post_backward left the gradient buffer stale), the
+    fused iteration on that model against the autograd one on a model built
+    from the same parameters: the bars of
+    test_fused_path_matches_autograd_path."""
+    T = _T()
+    m, s, gt = _densified_model(DENSIFY_SEED)
+    assert m.P != 3000 and m.P % 4 != 0, m.P
+    assert m.group_view(m.params, "rotation").data_ptr() % 16 != 0
+    assert m._grads_stale
+    ma = T.FlatGaussianModel({g: m.param[g].detach().clone() for g in T.GROUPS}, 3, spatial_lr_scale=5.0)
+    ma.active_sh_degree = m.active_sh_degree
+    out = []
+    for model, fused in ((m, True), (ma, False)):
+        pkg, terms = T.forward_backward(model, 3001, s, gt, fused=fused)
+        out.append((model, pkg, terms))
+    assert int((out[0][1]["radii"] > 0).sum()) > 100
+    _assert_fused_matches_autograd(out, m.active_sh_degree)
 
 
 def test_training_run_fits_a_target():
