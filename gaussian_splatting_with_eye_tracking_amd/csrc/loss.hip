@@ -6,7 +6,7 @@
 //
 // One workgroup per 32x32 output tile of one channel.  The tile's input with
 // a 10-px halo is staged in LDS once; the five separable 11-tap
-// correlations (x, y, x^2, y^2, xy) are evaluated on the 42x42 region the
+// correlations (x, y, x^2, y^2, xy; float64 accumulators) are evaluated on the 42x42 region the
 // adjoint needs, the SSIM map's three derivative maps are formed there
 // (zero outside the image), and the three adjoint correlations give the
 // gradient on the 32x32 tile.  HBM traffic: x and y read once (+ halo
@@ -25,7 +25,7 @@ constexpr int kT = 32;             // output tile
 constexpr int kR = 5;              // window radius
 constexpr int kIn = kT + 4 * kR;   // 52: input region
 constexpr int kMid = kT + 2 * kR;  // 42: region of the derivative maps
-constexpr int kThreads = 256;
+constexpr int kThreads = 1024;  // one workgroup per CU (109 KB of LDS): 4 waves per SIMD
 constexpr float kC1 = 0.01f * 0.01f;
 constexpr float kC2 = 0.03f * 0.03f;
 
@@ -40,16 +40,21 @@ __global__ void __launch_bounds__(kThreads) l1_ssim_kernel(const float* __restri
                                                            int H, int W, float lambda, float inv_n, Window11 win,
                                                            float* __restrict__ grad, float* __restrict__ partials) {
     const float* c_w = win.w;
-    // LDS plan (floats): [in_x | in_y] (2 x 52 x 52) then h5 (5 x 52 x 42);
+    // LDS plan: [in_x | in_y] (2 x 52 x 52 floats) then h5 (5 x 52 x 42 doubles);
     // after the first vertical pass the derivative maps (3 x 42 x 42) reuse
     // the in_* space and the second horizontal pass (3 x 42 x 32) reuses h5.
-    __shared__ float lds[2 * kIn * kIn + 5 * kIn * kMid];
+    // The five correlations are accumulated and kept in float64: over a flat
+    // region E[x^2] - mu^2 cancels to the rounding residue of its operands
+    // against C2 = 9e-4, and a float32 residue (1.5e-8 per rounding at
+    // E[x^2] = 0.49) biases the SSIM mean by several 1e-5.
+    __shared__ double lds_d[kIn * kIn + 5 * kIn * kMid];
     __shared__ float red[2][kThreads / 64];
+    float* lds = reinterpret_cast<float*>(lds_d);
     float* in_x = lds;
     float* in_y = lds + kIn * kIn;
-    float* h5 = lds + 2 * kIn * kIn;
-    float* g3 = lds;   // after pass 1
-    float* gh = h5;    // after the derivative maps
+    double* h5 = lds_d + kIn * kIn;
+    float* g3 = lds;                            // after pass 1
+    float* gh = reinterpret_cast<float*>(h5);   // after the derivative maps
     const int tid = threadIdx.x;
     const int ch = blockIdx.z;
     const int ox = blockIdx.x * kT, oy = blockIdx.y * kT;
@@ -71,15 +76,15 @@ __global__ void __launch_bounds__(kThreads) l1_ssim_kernel(const float* __restri
         const int r = i / kMid, c = i % kMid;
         const float* px = in_x + r * kIn + c;
         const float* py = in_y + r * kIn + c;
-        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
+        double a = 0.0, b = 0.0, aa = 0.0, bb = 0.0, ab = 0.0;
 #pragma unroll
         for (int t = 0; t < 11; t++) {
-            const float u = px[t], v = py[t], w = c_w[t];
-            a += w * u;
-            b += w * v;
-            aa += w * (u * u);
-            bb += w * (v * v);
-            ab += w * (u * v);
+            const double u = px[t], v = py[t], w = c_w[t];
+            a = fma(w, u, a);
+            b = fma(w, v, b);
+            aa = fma(w, u * u, aa);  // (u * u, v * v, u * v are exact in float64)
+            bb = fma(w, v * v, bb);
+            ab = fma(w, u * v, ab);
         }
         h5[0 * kIn * kMid + i] = a;
         h5[1 * kIn * kMid + i] = b;
@@ -93,17 +98,18 @@ __global__ void __launch_bounds__(kThreads) l1_ssim_kernel(const float* __restri
     for (int i = tid; i < kMid * kMid; i += kThreads) {
         const int r = i / kMid, c = i % kMid;
         const int gy = oy - kR + r, gx = ox - kR + c;
-        float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int t = 0; t < 11; t++) {
-            const float w = c_w[t];
+            const double w = c_w[t];
 #pragma unroll
-            for (int q = 0; q < 5; q++) s[q] += w * h5[q * kIn * kMid + (r + t) * kMid + c];
+            for (int q = 0; q < 5; q++) s[q] = fma(w, h5[q * kIn * kMid + (r + t) * kMid + c], s[q]);
         }
         float G1 = 0.f, G11 = 0.f, G12 = 0.f;
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            const float mu1 = s[0], mu2 = s[1];
-            const float s11 = s[2] - mu1 * mu1, s22 = s[3] - mu2 * mu2, s12 = s[4] - mu1 * mu2;
+            const float mu1 = (float)s[0], mu2 = (float)s[1];
+            const float s11 = (float)(s[2] - s[0] * s[0]), s22 = (float)(s[3] - s[1] * s[1]),
+                        s12 = (float)(s[4] - s[0] * s[1]);
             const float A = 2.f * mu1 * mu2 + kC1, B = 2.f * s12 + kC2;
             const float Cd = mu1 * mu1 + mu2 * mu2 + kC1, D = s11 + s22 + kC2;
             const float inv = 1.f / (Cd * D);

@@ -938,6 +938,9 @@ Tensor MarkVisible(Tensor& means3D_in, Tensor& viewmatrix_in, Tensor& projmatrix
 
 // knn/spatial.cu:14-24
 Tensor DistCUDA2(const Tensor& points_in) {
+    // the kernels read 3 * P floats with stride 3: any other shape would be
+    // read out of bounds ([P], [P, 2]) or with the wrong stride ([P, 4])
+    TORCH_CHECK(points_in.dim() == 2 && points_in.size(1) == 3, "points must be [P, 3], got ", points_in.sizes());
     const int P = (int)points_in.size(0);
     const at::OptionalDeviceGuard guard(device_of(points_in));
     Tensor means = torch::empty({P}, points_in.options().dtype(torch::kFloat32));
