@@ -395,8 +395,8 @@ Tensor AmrAccumulateStep(const Tensor& background, const Tensor& colors_in, int 
 using Grads8 = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
 // set_deterministic_backward: this thread's base backward bindings
-// (rasterize_gaussians_backward, _lean, _view_grads) call the deterministic C
-// entries, with the scratch from torch's allocator on the current stream.
+// (rasterize_gaussians_backward, _lean, _view_grads) run the deterministic
+// blend, with the scratch from torch's allocator on the current stream.
 // Persistent until set again; the Python wrappers set it around their call.
 thread_local bool t_det_backward = false;
 
@@ -405,141 +405,155 @@ Tensor det_scratch(int P, int R, const Tensor& like) {
     return torch::empty({(int64_t)n}, like.options().dtype(torch::kByte));
 }
 
-// amr_step 0: the base backward; != 0: the AMR (foveated) backward of
-// foveaStep amr_step (< 0: render_once, with `interpolate`).
-Grads8 BackwardImpl(int amr_step, bool interpolate, const Tensor& background, const Tensor& means3D_in,
-                    const Tensor& radii_in, const Tensor& colors_in, const Tensor& scales_in,
-                    const Tensor& rotations_in, const float scale_modifier, const Tensor& cov3D_precomp_in,
-                    const Tensor& viewmatrix_in, const Tensor& projmatrix_in, const float tan_fovx,
-                    const float tan_fovy, const Tensor& dL_dout_color_in, const Tensor& sh_in, const int degree,
-                    const Tensor& campos_in, const Tensor& geomBuffer, const int R, const Tensor& binningBuffer,
-                    const Tensor& imageBuffer, const bool debug, const bool lean,
-                    const Tensor* dL_ddepth_in = nullptr, const Tensor* dL_dalpha_in = nullptr,
-                    const std::optional<Tensor>& opacities_in = std::nullopt, const bool antialiasing = false) {
-    // (the aux binding: either map's cotangent, [1, H, W], or an empty tensor)
-    const bool aux = dL_ddepth_in && dL_dalpha_in && (dL_ddepth_in->numel() != 0 || dL_dalpha_in->numel() != 0);
-    const int P = (int)means3D_in.size(0);
-    const int H = (int)dL_dout_color_in.size(1);
-    const int W = (int)dL_dout_color_in.size(2);
-    const int M = sh_in.size(0) != 0 ? (int)sh_in.size(1) : 0;
-    const at::OptionalDeviceGuard guard(device_of(means3D_in));
-    auto opts = means3D_in.options();
-    // dL_dconic is never returned (base/rasterize_points.cu:185-196): not
-    // computed into memory at all.  lean (the autograd wrappers): the colour /
-    // covariance gradients only when their precomputed input was given --
-    // otherwise autograd drops them -- as empty tensors.
-    const bool want_colors = !lean || colors_in.numel() != 0;
-    const bool want_cov3D = !lean || cov3D_precomp_in.numel() != 0;
-    Tensor dL_dmeans3D = torch::empty({P, 3}, opts);
-    Tensor dL_dmeans2D = torch::empty({P, 3}, opts);
-    Tensor dL_dcolors = want_colors ? torch::empty({P, 3}, opts) : torch::empty({0}, opts);
-    Tensor dL_dopacity = torch::empty({P, 1}, opts);
-    Tensor dL_dcov3D = want_cov3D ? torch::empty({P, 6}, opts) : torch::empty({0}, opts);
-    Tensor dL_dsh = torch::empty({P, M, 3}, opts);
-    Tensor dL_dscales = torch::empty({P, 3}, opts);
-    Tensor dL_drotations = torch::empty({P, 4}, opts);
+// One backward's operands, contiguous, its cotangents, the forward's buffers,
+// its scalar arguments and its eight outputs, allocated here: filled once, by
+// backward_call, from the arguments the bindings share; BackwardImpl checks it
+// and makes the native call.
+struct BackwardCall {
+    Tensor bg, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos;
+    Tensor dL_dout;               // [3, H, W] always: it carries H and W
+    Tensor dL_ddepth, dL_dalpha;  // the aux bindings' map cotangents, [1, H, W]; empty: absent
+    Tensor opacities;             // the forward's input (the antialiased backward reads it); empty: not given
+    Tensor none;                  // an empty tensor, for what a call does not have
+    Tensor geom, binning, image;
+    Tensor dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations;
+    int P, M, W, H, R, degree;
+    float scale_modifier, tan_fovx, tan_fovy;
+    bool debug;
+    bool antialiasing = false;  // base backwards only
+    void* stream = nullptr;
+};
+
+// dL_dconic is never returned (base/rasterize_points.cu:185-196): not computed
+// into memory at all.  lean (the autograd wrappers): the colour / covariance
+// gradients only when their precomputed input was given -- otherwise autograd
+// drops them -- as empty tensors.
+BackwardCall backward_call(const bool lean, const Tensor& background, const Tensor& means3D, const Tensor& radii,
+                           const Tensor& colors, const Tensor& scales, const Tensor& rotations,
+                           const float scale_modifier, const Tensor& cov3D_precomp, const Tensor& viewmatrix,
+                           const Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                           const Tensor& dL_dout_color, const Tensor& sh, const int degree, const Tensor& campos,
+                           const Tensor& geomBuffer, const int R, const Tensor& binningBuffer,
+                           const Tensor& imageBuffer, const bool debug,
+                           const std::optional<Tensor>& opacities = std::nullopt, const bool antialiasing = false) {
+    BackwardCall c;
+    const int P = c.P = (int)means3D.size(0);
+    const int M = c.M = sh.size(0) != 0 ? (int)sh.size(1) : 0;
+    c.H = (int)dL_dout_color.size(1);
+    c.W = (int)dL_dout_color.size(2);
+    c.R = R;
+    c.degree = degree;
+    c.scale_modifier = scale_modifier;
+    c.tan_fovx = tan_fovx;
+    c.tan_fovy = tan_fovy;
+    c.debug = debug;
+    c.antialiasing = antialiasing;
+    const at::OptionalDeviceGuard guard(device_of(means3D));
+    auto opts = means3D.options();
+    c.none = torch::empty({0}, opts);
+    c.dL_dmeans3D = torch::empty({P, 3}, opts);
+    c.dL_dmeans2D = torch::empty({P, 3}, opts);
+    c.dL_dcolors = !lean || colors.numel() != 0 ? torch::empty({P, 3}, opts) : c.none;
+    c.dL_dopacity = torch::empty({P, 1}, opts);
+    c.dL_dcov3D = !lean || cov3D_precomp.numel() != 0 ? torch::empty({P, 6}, opts) : c.none;
+    c.dL_dsh = torch::empty({P, M, 3}, opts);
+    c.dL_dscales = torch::empty({P, 3}, opts);
+    c.dL_drotations = torch::empty({P, 4}, opts);
+    c.dL_ddepth = c.dL_dalpha = c.none;
+    c.opacities = opacities.has_value() ? *opacities : c.none;
+    if (P == 0) return c;  // nothing to do: the operands stay unset, unread
+    c.bg = background.contiguous();
+    c.means3D = means3D.contiguous();
+    c.radii = radii.contiguous();
+    c.colors = colors.contiguous();
+    c.scales = scales.contiguous();
+    c.rotations = rotations.contiguous();
+    c.cov3D_precomp = cov3D_precomp.contiguous();
+    c.viewmatrix = viewmatrix.contiguous();
+    c.projmatrix = projmatrix.contiguous();
+    c.dL_dout = dL_dout_color.contiguous();
+    c.sh = sh.contiguous();
+    c.campos = campos.contiguous();
+    c.geom = geomBuffer;
+    c.binning = binningBuffer;
+    c.image = imageBuffer;
+    c.stream = stream_of(c.means3D);
+    return c;
+}
+
+// The one place the backward bindings reach the library.  amr_step 0: the base
+// backward, always through the superset entry gs_rasterizer_backward_ex -- the
+// antialiasing flag, the deterministic blend (this thread's flag, with its
+// scratch) and the maps' cotangents are arguments of that one call; the
+// specialised C entries (gs_rasterizer_backward, _aux, _deterministic) build
+// the same call inside the library and remain for direct C and ctypes callers.
+// amr_step != 0: the AMR (foveated) backward of foveaStep amr_step (< 0:
+// render_once, with `interpolate`).
+Grads8 BackwardImpl(BackwardCall c, const int amr_step = 0, const bool interpolate = false) {
+    const int P = c.P, H = c.H, W = c.W;
+    const at::OptionalDeviceGuard guard(device_of(c.dL_dmeans3D));
     if (P != 0) {
-        const Tensor bg = background.contiguous(), means3D = means3D_in.contiguous(), radii = radii_in.contiguous(),
-                     colors = colors_in.contiguous(), scales = scales_in.contiguous(),
-                     rotations = rotations_in.contiguous(), cov3D_precomp = cov3D_precomp_in.contiguous(),
-                     viewmatrix = viewmatrix_in.contiguous(), projmatrix = projmatrix_in.contiguous(),
-                     dL_dout = dL_dout_color_in.contiguous(), sh = sh_in.contiguous(), campos = campos_in.contiguous();
-        require_device(means3D, "means3D");
-        require_like(dL_dout, means3D, "dL_dout_color", 3LL * H * W);
-        TORCH_CHECK(dL_dout.dim() == 3 && dL_dout.size(0) == 3, "dL_dout_color must be [3, H, W]");
+        const bool aux = c.dL_ddepth.numel() != 0 || c.dL_dalpha.numel() != 0;
+        require_device(c.means3D, "means3D");
+        require_like(c.dL_dout, c.means3D, "dL_dout_color", 3LL * H * W);
+        TORCH_CHECK(c.dL_dout.dim() == 3 && c.dL_dout.size(0) == 3, "dL_dout_color must be [3, H, W]");
         // (AMR steps >= 1 pass no radii: the geometry buffer keeps step 0's)
-        TORCH_CHECK(radii.numel() == P || (amr_step != 0 && radii.numel() == 0), "radii must have P elements");
-        require_like(radii, means3D, "radii", P, torch::kInt32);
-        const Tensor no_opacity = torch::empty({0}, opts);
-        check_operands(means3D, P, bg, colors, no_opacity, scales, rotations, cov3D_precomp, viewmatrix,
-                       projmatrix, sh, campos);
-        for (const Tensor* bt : {&geomBuffer, &binningBuffer, &imageBuffer})
-            require_like(*bt, means3D, "geometry / binning / image buffer", -1, torch::kByte);
+        TORCH_CHECK(c.radii.numel() == P || (amr_step != 0 && c.radii.numel() == 0), "radii must have P elements");
+        require_like(c.radii, c.means3D, "radii", P, torch::kInt32);
+        check_operands(c.means3D, P, c.bg, c.colors, c.none, c.scales, c.rotations, c.cov3D_precomp, c.viewmatrix,
+                       c.projmatrix, c.sh, c.campos);
+        for (const Tensor* bt : {&c.geom, &c.binning, &c.image})
+            require_like(*bt, c.means3D, "geometry / binning / image buffer", -1, torch::kByte);
+        // (the opacities are read, and so checked, under the flag only)
+        const Tensor opac = c.antialiasing ? c.opacities.contiguous() : c.none;
+        TORCH_CHECK(amr_step == 0 || !c.antialiasing, "the AMR rasterizer has no antialiased form");
+        TORCH_CHECK(!c.antialiasing || opac.numel() != 0,
+                    "rasterize_gaussians_backward: antialiasing needs the forward's opacities");
+        TORCH_CHECK(amr_step == 0 || !aux, "the AMR backward takes no depth / alpha cotangents");
+        TORCH_CHECK(!(aux && t_det_backward),
+                    "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
+                    "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
+                    "for this call");
+        require_like(opac, c.means3D, "opacities", P);
+        const Tensor dd = c.dL_ddepth.contiguous(), da = c.dL_dalpha.contiguous();
+        require_like(dd, c.means3D, "dL_ddepth", (int64_t)H * W);
+        require_like(da, c.means3D, "dL_dalpha", (int64_t)H * W);
         int rc;
-        if (antialiasing) {
-            // the backward of an antialiased forward: the superset entry, whatever else the call is
-            TORCH_CHECK(amr_step == 0, "the AMR rasterizer has no antialiased form");
-            TORCH_CHECK(opacities_in.has_value() && opacities_in->numel() != 0,
-                        "rasterize_gaussians_backward: antialiasing needs the forward's opacities");
-            TORCH_CHECK(!(aux && t_det_backward),
-                        "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
-                        "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
-                        "for this call");
-            const Tensor opac = opacities_in->contiguous();
-            require_like(opac, means3D, "opacities", P);
-            const Tensor dd = aux ? dL_ddepth_in->contiguous() : no_opacity;
-            const Tensor da = aux ? dL_dalpha_in->contiguous() : no_opacity;
-            if (dd.numel()) require_like(dd, means3D, "dL_ddepth", (int64_t)H * W);
-            if (da.numel()) require_like(da, means3D, "dL_dalpha", (int64_t)H * W);
-            Tensor scratch = t_det_backward ? det_scratch(P, R, means3D) : torch::empty({0}, opts);
+        if (amr_step == 0) {
+            const bool det = t_det_backward;
+            const Tensor scratch = det ? det_scratch(P, c.R, c.means3D) : c.none;
+            // A cotangent without pixels (H * W == 0) is a null pointer.  The plain
+            // entries take one and return the gradients of no image; the superset
+            // entry refuses a call whose every cotangent is null, as an antialiased
+            // call always was.  No pixel is read, so any other call without pixels
+            // hands over a non-null pointer instead and gets what it always got.
+            const float* dL_dpix = c.dL_dout.numel() != 0 || c.antialiasing ? fptr(c.dL_dout) : fptr(c.means3D);
             rc = gs_rasterizer_backward_ex(
-                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(opac), fptr(scales),
-                scale_modifier, fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos),
-                tan_fovx, tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
-                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
-                fptr(dL_dout), fptr(dd), fptr(da), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
-                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
-                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
-                fptr_mut(dL_drotations), 1, t_det_backward ? 1 : 0,
-                scratch.numel() ? reinterpret_cast<char*>(scratch.data_ptr()) : nullptr, (size_t)scratch.numel(), debug,
-                stream_of(means3D));
-        } else if (aux) {
-            TORCH_CHECK(amr_step == 0, "the AMR backward takes no depth / alpha cotangents");
-            TORCH_CHECK(!t_det_backward,
-                        "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
-                        "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
-                        "for this call");
-            const Tensor dd = dL_ddepth_in->contiguous(), da = dL_dalpha_in->contiguous();
-            if (dd.numel()) require_like(dd, means3D, "dL_ddepth", (int64_t)H * W);
-            if (da.numel()) require_like(da, means3D, "dL_dalpha", (int64_t)H * W);
-            rc = gs_rasterizer_backward_aux(
-                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
-                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
-                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
-                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
-                fptr(dL_dout), fptr(dd), fptr(da), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
-                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
-                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
-                fptr_mut(dL_drotations), debug, stream_of(means3D));
-        } else if (amr_step == 0 && t_det_backward) {
-            Tensor scratch = det_scratch(P, R, means3D);
-            rc = gs_rasterizer_backward_deterministic(
-                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
-                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
-                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
-                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
-                fptr(dL_dout), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
-                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
-                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
-                fptr_mut(dL_drotations), scratch.numel() ? reinterpret_cast<char*>(scratch.data_ptr()) : nullptr,
-                (size_t)scratch.numel(), debug, stream_of(means3D));
-        } else if (amr_step == 0) {
-            rc = gs_rasterizer_backward(
-                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
-                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
-                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
-                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
-                fptr(dL_dout), fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity),
-                want_colors ? fptr_mut(dL_dcolors) : nullptr, fptr_mut(dL_dmeans3D),
-                want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh),
-                fptr_mut(dL_dscales), fptr_mut(dL_drotations), debug, stream_of(means3D));
+                P, c.degree, c.M, c.R, fptr(c.bg), W, H, fptr(c.means3D), fptr(c.sh), fptr(c.colors), fptr(opac),
+                fptr(c.scales), c.scale_modifier, fptr(c.rotations), fptr(c.cov3D_precomp), fptr(c.viewmatrix),
+                fptr(c.projmatrix), fptr(c.campos), c.tan_fovx, c.tan_fovy, c.radii.data_ptr<int>(),
+                reinterpret_cast<char*>(c.geom.data_ptr()), reinterpret_cast<char*>(c.binning.data_ptr()),
+                reinterpret_cast<char*>(c.image.data_ptr()), dL_dpix, fptr(dd), fptr(da), fptr_mut(c.dL_dmeans2D),
+                nullptr, fptr_mut(c.dL_dopacity), fptr_mut(c.dL_dcolors), fptr_mut(c.dL_dmeans3D), fptr_mut(c.dL_dcov3D),
+                fptr_mut(c.dL_dsh), fptr_mut(c.dL_dscales), fptr_mut(c.dL_drotations), c.antialiasing ? 1 : 0,
+                det ? 1 : 0, bptr(scratch), (size_t)scratch.numel(), c.debug, c.stream);
         } else {
-            TORCH_CHECK(imageBuffer.numel() > 0, "the AMR backward needs the image buffer of the forward");
-            Tensor scratch = interpolate ? torch::empty_like(dL_dout) : torch::empty({0}, opts);
+            TORCH_CHECK(c.image.numel() > 0, "the AMR backward needs the image buffer of the forward");
+            Tensor scratch = interpolate ? torch::empty_like(c.dL_dout) : c.none;
             rc = gs_amr_rasterizer_backward(
-                P, degree, M, R, fptr(bg), W, H, fptr(means3D), fptr(sh), fptr(colors), fptr(scales), scale_modifier,
-                fptr(rotations), fptr(cov3D_precomp), fptr(viewmatrix), fptr(projmatrix), fptr(campos), tan_fovx,
-                tan_fovy, radii.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
-                reinterpret_cast<char*>(binningBuffer.data_ptr()), reinterpret_cast<char*>(imageBuffer.data_ptr()),
-                amr_step, interpolate ? 1 : 0, fptr(dL_dout), interpolate ? fptr_mut(scratch) : nullptr,
-                fptr_mut(dL_dmeans2D), nullptr, fptr_mut(dL_dopacity), want_colors ? fptr_mut(dL_dcolors) : nullptr,
-                fptr_mut(dL_dmeans3D), want_cov3D ? fptr_mut(dL_dcov3D) : nullptr, fptr_mut(dL_dsh), fptr_mut(dL_dscales),
-                fptr_mut(dL_drotations), debug, stream_of(means3D));
+                P, c.degree, c.M, c.R, fptr(c.bg), W, H, fptr(c.means3D), fptr(c.sh), fptr(c.colors), fptr(c.scales),
+                c.scale_modifier, fptr(c.rotations), fptr(c.cov3D_precomp), fptr(c.viewmatrix), fptr(c.projmatrix),
+                fptr(c.campos), c.tan_fovx, c.tan_fovy, c.radii.data_ptr<int>(),
+                reinterpret_cast<char*>(c.geom.data_ptr()), reinterpret_cast<char*>(c.binning.data_ptr()),
+                reinterpret_cast<char*>(c.image.data_ptr()), amr_step, interpolate ? 1 : 0, fptr(c.dL_dout),
+                fptr_mut(scratch), fptr_mut(c.dL_dmeans2D), nullptr, fptr_mut(c.dL_dopacity), fptr_mut(c.dL_dcolors),
+                fptr_mut(c.dL_dmeans3D), fptr_mut(c.dL_dcov3D), fptr_mut(c.dL_dsh), fptr_mut(c.dL_dscales),
+                fptr_mut(c.dL_drotations), c.debug, c.stream);
         }
         check(rc, amr_step ? "amr_rasterize_gaussians_backward" : "rasterize_gaussians_backward");
     }
-    return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                           dL_drotations);
+    return std::make_tuple(c.dL_dmeans2D, c.dL_dcolors, c.dL_dopacity, c.dL_dmeans3D, c.dL_dcov3D, c.dL_dsh,
+                           c.dL_dscales, c.dL_drotations);
 }
 
 // base/rasterize_points.cu:117-196
@@ -551,10 +565,10 @@ Grads8 RasterizeGaussiansBackward(const Tensor& background, const Tensor& means3
                                   const Tensor& campos, const Tensor& geomBuffer, const int R,
                                   const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
                                   const std::optional<Tensor>& opacities, const bool antialiasing) {
-    return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
-                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, false, nullptr, nullptr, opacities,
-                        antialiasing);
+    return BackwardImpl(backward_call(false, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, opacities,
+                                      antialiasing));
 }
 
 // The same, for the autograd wrappers: grad_colors_precomp / grad_cov3Ds_precomp
@@ -567,10 +581,10 @@ Grads8 RasterizeGaussiansBackwardLean(const Tensor& background, const Tensor& me
                                       const int degree, const Tensor& campos, const Tensor& geomBuffer, const int R,
                                       const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
                                       const std::optional<Tensor>& opacities, const bool antialiasing) {
-    return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
-                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, true, nullptr, nullptr, opacities,
-                        antialiasing);
+    return BackwardImpl(backward_call(true, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, opacities,
+                                      antialiasing));
 }
 
 // The backward of rasterize_gaussians_aux: the lean binding's arguments with
@@ -588,10 +602,13 @@ Grads8 RasterizeGaussiansBackwardAux(const Tensor& background, const Tensor& mea
                                      const Tensor& campos, const Tensor& geomBuffer, const int R,
                                      const Tensor& binningBuffer, const Tensor& imageBuffer, const bool debug,
                                      const std::optional<Tensor>& opacities, const bool antialiasing) {
-    return BackwardImpl(0, false, background, means3D, radii, colors, scales, rotations, scale_modifier,
-                        cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                        geomBuffer, R, binningBuffer, imageBuffer, debug, kLean, &dL_ddepth, &dL_dalpha, opacities,
-                        antialiasing);
+    BackwardCall c = backward_call(kLean, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                   cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                   degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, opacities,
+                                   antialiasing);
+    c.dL_ddepth = dL_ddepth;
+    c.dL_dalpha = dL_dalpha;
+    return BackwardImpl(std::move(c));
 }
 
 // The AMR backward (an extension: the reference's is unreachable): the
@@ -609,9 +626,10 @@ Grads8 AmrRasterizeGaussiansBackward(const Tensor& background, const Tensor& mea
     // (the AMR blend backward keeps its float atomics: raises, or warns, under
     // torch.use_deterministic_algorithms, as torch's own such ops do)
     if (t_det_backward) at::globalContext().alertNotDeterministic("amr_rasterize_gaussians_backward");
-    return BackwardImpl(foveaStep, interpolate_image, background, means3D, radii, colors, scales, rotations,
-                        scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
-                        degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug, true);
+    return BackwardImpl(backward_call(true, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                      degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug),
+                        foveaStep, interpolate_image);
 }
 
 // Data-parallel stage 1 (gsplat_amd.h): blend backward of one view -> its

@@ -118,7 +118,33 @@ class _DeterministicScope:
         return False
 
 
-class _RasterizeGaussians(torch.autograd.Function):
+def native_forward_args(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """The positional arguments of ``_C.rasterize_gaussians`` / ``_aux``: the one
+    place that knows their order."""
+    s = settings
+    return (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
+            s.campos, s.prefiltered, s.debug, _antialiasing(s))
+
+
+def native_backward_args(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                         radii, geomBuffer, binningBuffer, imgBuffer, num_rendered, grad_color, grad_maps=None):
+    """The positional arguments of ``_C.rasterize_gaussians_backward`` / ``_lean``
+    or, with ``grad_maps = (dL_ddepth, dL_dalpha)``, of ``_aux`` / ``_aux_lean``.
+    ``opacities``: the forward's input, read by the antialiased backward only."""
+    s = settings
+    return ((s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_color) + tuple(grad_maps or ()) +
+            (sh, s.sh_degree, s.campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, s.debug, opacities,
+             _antialiasing(s)))
+
+
+class _RasterizeBase(torch.autograd.Function):
+    """What _RasterizeGaussians and _RasterizeGaussiansAux share: the one-shot
+    forward-only hint around ``apply``, the native forward with what the
+    backward needs saved, and the lean native backward with its gradients put
+    into input order."""
+
     @classmethod
     def apply(cls, *args):
         hinted = _hint_forward_only(args[:8])
@@ -128,71 +154,60 @@ class _RasterizeGaussians(torch.autograd.Function):
             _clear_hint(hinted)
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
-        s = raster_settings
-        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug, _antialiasing(s))
-        num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _call(
-            _C.rasterize_gaussians, args, s.debug, "snapshot_fw.dump", "forward")
+    def native_forward(ctx, fn, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, s):
+        """Returns ``fn``'s outputs between num_rendered and the three buffers:
+        (color, radii) or (color, depth, alpha, radii)."""
+        operands = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        num_rendered, *outs, geomBuffer, binningBuffer, imgBuffer = _call(
+            fn, native_forward_args(s, *operands), s.debug, "snapshot_fw.dump", "forward")
         ctx.raster_settings = s
         ctx.num_rendered = num_rendered
-        # (opacities: read by the antialiased backward only)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, opacities)
+        ctx.save_for_backward(*operands, outs[-1], geomBuffer, binningBuffer, imgBuffer)
         # radii (int32) never carries a gradient: without this autograd fills a
         # zero int tensor of P elements for it on every backward (~6 us at 1M)
         ctx.set_materialize_grads(False)
+        return outs
+
+    @staticmethod
+    def native_backward(ctx, grad_out_color, grad_maps=None):
+        s = ctx.raster_settings
+        fn = _C.rasterize_gaussians_backward_lean if grad_maps is None else _C.rasterize_gaussians_backward_aux_lean
+        args = native_backward_args(s, *ctx.saved_tensors, ctx.num_rendered, grad_out_color, grad_maps)
+        with _DeterministicScope():
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
+             grad_scales, grad_rotations) = _call(fn, args, s.debug, "snapshot_bw.dump", "backward")
+        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
+                grad_rotations, grad_cov3Ds_precomp, None)
+
+
+class _RasterizeGaussians(_RasterizeBase):
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        color, radii = _RasterizeBase.native_forward(
+            ctx, _C.rasterize_gaussians, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+            raster_settings)
         return color, radii
 
     @staticmethod
     def backward(ctx, grad_out_color, _):
         if grad_out_color is None:  # the image took no part in the loss
             return (None,) * 9
-        s = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer, opacities) = ctx.saved_tensors
-        args = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, sh, s.sh_degree, s.campos,
-                geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug, opacities, _antialiasing(s))
-        with _DeterministicScope():
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _call(_C.rasterize_gaussians_backward_lean, args, s.debug,
-                                                  "snapshot_bw.dump", "backward")
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None)
+        return _RasterizeBase.native_backward(ctx, grad_out_color)
 
 
-class _RasterizeGaussiansAux(torch.autograd.Function):
+class _RasterizeGaussiansAux(_RasterizeBase):
     """_RasterizeGaussians with the depth and alpha maps as two more
     differentiable outputs.  A backward that got neither map's cotangent is
     the plain lean backward; one that got either has no deterministic form
     and raises under the deterministic mode rather than use atomics."""
 
-    @classmethod
-    def apply(cls, *args):
-        hinted = _hint_forward_only(args[:8])
-        try:
-            return super().apply(*args)
-        finally:
-            _clear_hint(hinted)
-
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
-        s = raster_settings
-        args = (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-                s.campos, s.prefiltered, s.debug, _antialiasing(s))
-        num_rendered, color, depth, alpha, radii, geomBuffer, binningBuffer, imgBuffer = _call(
-            _C.rasterize_gaussians_aux, args, s.debug, "snapshot_fw.dump", "forward")
-        ctx.raster_settings = s
-        ctx.num_rendered = num_rendered
-        # (opacities: read by the antialiased backward only)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, opacities)
-        ctx.set_materialize_grads(False)
+        color, depth, alpha, radii = _RasterizeBase.native_forward(
+            ctx, _C.rasterize_gaussians_aux, means3D, sh, colors_precomp, opacities, scales, rotations,
+            cov3Ds_precomp, raster_settings)
         ctx.mark_non_differentiable(radii)
         return color, radii, depth, alpha
 
@@ -200,9 +215,6 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
     def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
         if grad_out_color is None and grad_depth is None and grad_alpha is None:
             return (None,) * 9
-        s = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer, opacities) = ctx.saved_tensors
         aux = grad_depth is not None or grad_alpha is not None
         if aux and deterministic_requested():
             raise RuntimeError(
@@ -210,26 +222,15 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
                 "cotangents (a deterministic aux backward is not built); call set_deterministic(False) or keep "
                 "the depth and alpha maps out of the loss")
         if grad_out_color is None:  # (the native call takes H and W from it)
+            s, means3D = ctx.raster_settings, ctx.saved_tensors[0]
             grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=means3D.dtype,
                                          device=means3D.device)
-        head = (s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color)
-        tail = (sh, s.sh_degree, s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.debug,
-                opacities, _antialiasing(s))
-        with _DeterministicScope():
-            if aux:
-                none = grad_out_color.new_empty(0)
-                args = head + (none if grad_depth is None else grad_depth,
-                               none if grad_alpha is None else grad_alpha) + tail
-                grads = _call(_C.rasterize_gaussians_backward_aux_lean, args, s.debug, "snapshot_bw.dump",
-                              "backward")
-            else:
-                grads = _call(_C.rasterize_gaussians_backward_lean, head + tail, s.debug, "snapshot_bw.dump",
-                              "backward")
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-         grad_scales, grad_rotations) = grads
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None)
+        if not aux:
+            return _RasterizeBase.native_backward(ctx, grad_out_color)
+        none = grad_out_color.new_empty(0)
+        return _RasterizeBase.native_backward(
+            ctx, grad_out_color, (none if grad_depth is None else grad_depth,
+                                  none if grad_alpha is None else grad_alpha))
 
 
 class _ReferenceSettings(NamedTuple):

@@ -40,7 +40,8 @@ from torch import nn
 
 from . import _C
 from .losses import l1_ssim_loss_terms
-from .rasterization import GaussianRasterizationSettings, GaussianRasterizer
+from .rasterization import (GaussianRasterizationSettings, GaussianRasterizer, native_backward_args,
+                            native_forward_args)
 
 GROUPS: Tuple[str, ...] = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
 BETAS = (0.9, 0.999)
@@ -366,15 +367,12 @@ class FlatGaussianModel:
                     a["opacities"], a["scales"], a["rotations"])
         e = torch.empty(0, device=self.device)
         xyz = raw["xyz"]
-        num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(
-            s.bg, xyz, e, a["opacities"], a["scales"], a["rotations"], s.scale_modifier, e, s.viewmatrix,
-            s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, a["shs"], s.sh_degree, s.campos,
-            s.prefiltered, s.debug, bool(getattr(s, "antialiasing", False)))
+        operands = (xyz, a["shs"], e, a["opacities"], a["scales"], a["rotations"], e)
+        num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(*native_forward_args(s, *operands))
         out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
-        (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = _C.rasterize_gaussians_backward_lean(
-            s.bg, xyz, radii, e, a["scales"], a["rotations"], s.scale_modifier, e, s.viewmatrix, s.projmatrix,
-            s.tanfovx, s.tanfovy, d_image, a["shs"], s.sh_degree, s.campos, geom, num_rendered, binning, img,
-            s.debug, a["opacities"], bool(getattr(s, "antialiasing", False)))
+        (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = \
+            _C.rasterize_gaussians_backward_lean(*native_backward_args(
+                s, *operands, radii, geom, binning, img, num_rendered, d_image))
         gv = {g: self.group_view(self.grads, g) for g in GROUPS}
         _C.activation_backward(d_shs, d_opac, d_scales, d_rot, d_means3D, raw["opacity"], raw["scaling"],
                                raw["rotation"], gv["xyz"], gv["f_dc"], gv["f_rest"], gv["opacity"], gv["scaling"],
@@ -403,10 +401,9 @@ def render_and_backward_views(model: FlatGaussianModel, settings: GaussianRaster
                 a["opacities"], a["scales"], a["rotations"])
     e = torch.empty(0, device=model.device)
     xyz = raw["xyz"]
-    fwd = _C.rasterize_gaussians(
-        s.bg, xyz, e, a["opacities"], a["scales"], a["rotations"], s.scale_modifier, e, s.viewmatrix,
-        s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, a["shs"], s.sh_degree, s.campos,
-        s.prefiltered, s.debug)
+    # (the antialiasing flag the builder passes is always false: refuse_antialiasing ran)
+    fwd = _C.rasterize_gaussians(*native_forward_args(
+        s, xyz, a["shs"], e, a["opacities"], a["scales"], a["rotations"], e))
     num_rendered, color, radii, geom, binning, img = fwd
     out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
     st = (model.xyz_gradient_accum, model.denom, model.max_radii2D) if stats else None

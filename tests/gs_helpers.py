@@ -2,6 +2,7 @@
 and tolerance checks with the tolerances of BASELINE.json's north_star."""
 from __future__ import annotations
 
+import contextlib
 import glob
 import io
 import os
@@ -248,6 +249,150 @@ def scene_tensors(sc, device="cuda", requires_grad=False):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device).requires_grad_(requires_grad)  # noqa: E731
     return dict(means3D=t(sc.means3D), opacities=t(sc.opacities), shs=t(sc.shs), scales=t(sc.scales),
                 rotations=t(sc.rotations))
+
+
+# (name, P, W, H, seed): the shapes the parity and the deterministic tests share
+PARITY_CASES = [
+    ("g1_64_32x32", 64, 32, 32, 3),
+    ("cfg1_10k_256", 10000, 256, 256, 0),
+    ("ragged_3k_250x130", 3000, 250, 130, 7),
+    ("dense_20k_128", 20000, 128, 128, 11),  # large tiles: exercises the merge-sort path
+    ("grid_17k_tiles", 3000, 2112, 2080, 5),  # T = 17160 > kLdsTiles: device-atomic binning path
+]
+
+
+_OPERAND_KEYS = ("means3D", "shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp")
+
+
+def _operands(t):
+    """A tensor dict's operands in the builders' order (colours / covariance not named: absent)."""
+    import torch
+    return tuple(t.get(k, torch.Tensor([])) for k in _OPERAND_KEYS)
+
+
+def _cuda(a):
+    import torch
+    return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def native_forward(sc, cam, colors_precomp=None, cov3D_precomp=None, bg=(0.0, 0.0, 0.0), keep_scales=False, *,
+                   aux=False, antialiasing=False, settings=None, tensors=None, trailing=True, **settings_kw):
+    """The raw forward binding (`aux`: rasterize_gaussians_aux) on a scene:
+    `(settings, tensors, out)` after a synchronise.  SHs unless colours are
+    given; scales / rotations unless a covariance is (`keep_scales`: both).
+    `settings` / `tensors`: the caller's (torch_settings / scene_tensors
+    otherwise, with `bg` and `settings_kw`); the tensors returned are the
+    operands the call was given (_OPERAND_KEYS; an empty tensor: absent), and
+    native_backward reads them.  trailing=False: the reference's argument list, without the trailing
+    extension argument."""
+    import torch
+    from gaussian_splatting_with_eye_tracking_amd import _C, rasterization as R
+    s = torch_settings(cam, bg=bg, **settings_kw) if settings is None else settings
+    if antialiasing:
+        s = s._replace(antialiasing=True)
+    t = scene_tensors(sc) if tensors is None else dict(tensors)
+    e = torch.Tensor([])
+    if colors_precomp is not None:
+        t.update(shs=e, colors_precomp=_cuda(colors_precomp))
+    if cov3D_precomp is not None:
+        t["cov3D_precomp"] = _cuda(cov3D_precomp)
+        if not keep_scales:
+            t.update(scales=e, rotations=e)
+    args = R.native_forward_args(s, *_operands(t))
+    out = (_C.rasterize_gaussians_aux if aux else _C.rasterize_gaussians)(*(args if trailing else args[:-1]))
+    torch.cuda.synchronize()
+    return s, t, out
+
+
+def native_backward(fwd, dpix, *, lean=False, det=None, aux=None, antialiasing=None, debug=False, trailing=True):
+    """The raw backward binding on one native_forward (or on any `(settings,
+    tensors, out)` of a forward), with the thread's
+    deterministic flag at `det` for the call (None: as it is): the eight
+    gradients, after a synchronise.  aux=(dL_ddepth, dL_dalpha), either None
+    for an empty tensor: the _aux binding.  antialiasing: the flag passed
+    (default: the forward's).
+    trailing=False: the reference's argument list, without the trailing
+    opacities and flag."""
+    import torch
+    from gaussian_splatting_with_eye_tracking_amd import _C, rasterization as R
+    s, t, out = fwd
+    s = s._replace(debug=debug)
+    if antialiasing is not None:
+        s = s._replace(antialiasing=antialiasing)
+    maps = None if aux is None else tuple(torch.Tensor([]).cuda() if a is None else _cuda(a) for a in aux)
+    args = R.native_backward_args(s, *_operands(t), out[-4], *out[-3:], out[0], _cuda(dpix), maps)
+    fn = getattr(_C, "rasterize_gaussians_backward" + ("" if aux is None else "_aux") + ("_lean" if lean else ""))
+    prev = _C.get_deterministic_backward()
+    _C.set_deterministic_backward(prev if det is None else det)
+    try:
+        g = fn(*(args if trailing else args[:-2]))
+        torch.cuda.synchronize()
+    finally:
+        _C.set_deterministic_backward(prev)
+    return list(g)
+
+
+@contextlib.contextmanager
+def tuning(**kv):
+    """The library's tunings set to `kv` inside the block, and what they were put back after it."""
+    from gaussian_splatting_with_eye_tracking_amd import _C
+    was = {k: _C.get_tuning(k) for k in kv}
+    try:
+        for k, v in kv.items():
+            _C.set_tuning(k, v)
+        yield
+    finally:
+        for k, v in was.items():
+            _C.set_tuning(k, v)
+        assert {k: _C.get_tuning(k) for k in was} == was
+
+
+def oracle_forward(sc, cam, colors_precomp=None, cov3D_precomp=None, bg=(0.0, 0.0, 0.0), keep_scales=False):
+    """The oracle's forward of native_forward's scene: (settings, result, the operand keywords)."""
+    import oracle as O
+    s = O.settings_from_camera(cam, bg=bg)
+    both = cov3D_precomp is None or keep_scales
+    kw = dict(shs=sc.shs if colors_precomp is None else None, colors_precomp=colors_precomp,
+              scales=sc.scales if both else None,
+              rotations=sc.rotations if both else None, cov3D_precomp=cov3D_precomp)
+    return s, O.forward(s, sc.means3D, sc.opacities, **kw), kw
+
+
+def assert_same_buffers(C, a, b, P, K, W, H, vis):
+    """Every field of the two forwards' geometry / image / binning buffers
+    (per-Gaussian records of the visible Gaussians: the culled ones' are never
+    written; header: the words a forward defines whatever the binning
+    buffer's capacity)."""
+    import torch
+    da = C.parse_buffers(*a, P, K, W, H, 16)
+    db = C.parse_buffers(*b, P, K, W, H, 16)
+    assert set(da) == set(db)
+    per_gaussian = {"depths", "means2D", "conic_opacity", "rgb", "clamped_bits", "cov3D"}
+    # AMR / scratch words, and the geometry buffer's own radii slot: the
+    # binding hands the forward its radii tensor (compared by the caller), so
+    # the slot is never written
+    skip = {"hdr", "levels", "levels_last", "levels_current", "pv", "tile_count", "radii"}
+    for k in da:
+        if k in skip:
+            continue
+        if k in per_gaussian:
+            if k != "cov3D":  # (written on request only)
+                assert torch.equal(da[k][vis], db[k][vis]), k
+        else:
+            assert torch.equal(da[k], db[k]), k
+    for w in (0, 2, 3, 7):  # K, the tile statistics, the drgb flag
+        assert int(da["hdr"][w]) == int(db["hdr"][w]), w
+    assert (int(da["hdr"][6]) != 0) == (int(db["hdr"][6]) != 0)  # hit codes left (compared above)
+
+
+def raw_from_scene(sc, device="cuda"):
+    """The raw (pre-activation) parameter groups of a synthetic scene, as training.FlatGaussianModel takes them."""
+    import torch
+    from gaussian_splatting_with_eye_tracking_amd import ply
+    g = ply.from_activated(sc.means3D, sc.opacities, sc.scales, sc.rotations, sc.shs)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)  # noqa: E731
+    return {"xyz": t(g.xyz), "f_dc": t(g.features_dc), "f_rest": t(g.features_rest), "opacity": t(g.opacity),
+            "scaling": t(g.scaling), "rotation": t(g.rotation)}
 
 
 def image_l1(a, b) -> float:

@@ -34,39 +34,18 @@ from gaussian_splatting_with_eye_tracking_amd import synthetic as S
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-         "dL_drotations"]
+NAMES = AR.NAMES
 # scenes 1-3 in the three variants of test_oracle_autograd, scene 4 (mixed floor), and the remaining
 # per-Gaussian kernel forms on scene 2
 CASES = ([(k, v) for k in (1, 2, 3) for v in ("sh", "colors", "cov")] + [(4, "sh")] +
          [(2, v) for v in ("sh_nodrgb", "sh_m4", "sh_m4_cov", "colors_cov")])
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _variant_kw(sc, variant, seed):
-    """The oracle's keywords of a variant, and its SH degree."""
-    P = sc.means3D.shape[0]
-    shs, deg = (np.ascontiguousarray(sc.shs[:, :4]), 1) if "m4" in variant else (sc.shs, 3)
-    kw = {}
-    if variant.startswith("colors"):
-        kw["colors_precomp"] = np.random.default_rng(seed + 9).uniform(0, 1, (P, 3)).astype(np.float32)
-    else:
-        kw["shs"] = shs
-    if variant.endswith("cov"):
-        kw["cov3D_precomp"] = AR.cov3d32(sc.scales, sc.rotations)  # (the oracle's cov3D bits: test_antialias_reference)
-    else:
-        kw["scales"], kw["rotations"] = sc.scales, sc.rotations
-    return kw, deg
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(scene, variant):
     """One composite reference per case, shared and left unchanged."""
     sc, cam, dpix = AR.make_case(scene)
-    kw, deg = _variant_kw(sc, variant, AR.SCENES[scene][3])
+    kw, deg = AR.variant_kw(sc, variant, AR.SCENES[scene][3])
     ref = AR.reference_forward(cam, sc.means3D, sc.opacities, kw, sh_degree=deg)
     return sc, cam, dpix, kw, deg, ref
 
@@ -77,51 +56,13 @@ def _reference_grads(scene, variant):
     return AR.reference_backward(ref, dpix), AR.reference_allowance(ref, dpix)
 
 
-def _operands(sc, cam, kw, deg, antialiasing):
-    s = G.torch_settings(cam, bg=AR.BG, sh_degree=deg)._replace(antialiasing=antialiasing)
-    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
-    e = torch.Tensor([])
-    t = {k: (cu(kw[k]) if k in kw else e) for k in ("shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")}
-    t["means3D"], t["opacities"] = cu(sc.means3D), cu(sc.opacities)
-    return s, t
-
-
 def _forward(C, s, t, aux=False, trailing=True):
-    fn = C.rasterize_gaussians_aux if aux else C.rasterize_gaussians
-    args = (s.bg, t["means3D"], t["colors_precomp"], t["opacities"], t["scales"], t["rotations"], s.scale_modifier,
-            t["cov3D_precomp"], s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-            t["shs"], s.sh_degree, s.campos, s.prefiltered, s.debug)
-    out = fn(*args, bool(s.antialiasing)) if trailing else fn(*args)
-    torch.cuda.synchronize()
-    return out
+    return G.native_forward(None, None, settings=s, tensors=t, aux=aux, trailing=trailing)[2]
 
 
 def _backward(C, s, t, radii, geom, K, binning, img, dpix, antialiasing=None, debug=False, aux=None):
-    aa = bool(s.antialiasing) if antialiasing is None else antialiasing
-    head = (s.bg, t["means3D"], radii, t["colors_precomp"], t["scales"], t["rotations"], s.scale_modifier,
-            t["cov3D_precomp"], s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, torch.from_numpy(dpix).cuda())
-    tail = (t["shs"], s.sh_degree, s.campos, geom, K, binning, img, debug, t["opacities"], aa)
-    if aux is None:
-        g = C.rasterize_gaussians_backward(*head, *tail)
-    else:
-        g = C.rasterize_gaussians_backward_aux(*head, *(torch.from_numpy(a).cuda() for a in aux), *tail)
-    torch.cuda.synchronize()
-    return g
-
-
-def _check_grads(case, grads, rg, al, sc, cam, fwd):
-    for n, g in zip(NAMES, grads):
-        gg = g.cpu().numpy()
-        assert np.all(np.isfinite(gg)), n
-        if n not in rg or not rg[n].any():  # an absent input: an empty or all-zero gradient
-            assert gg.size == 0 or not gg.any(), n
-            continue
-        assert gg.shape == rg[n].shape, n
-        err = G.rel_err(gg, rg[n])
-        print(f"{case} {n}: rel err {err:.3e}")
-        assert err < G.GRAD_REL_TOL, (n, err)
-    G.assert_grads_elementwise(case, NAMES, grads, {n: v for n, v in rg.items() if n in NAMES and v.any()}, sc, cam,
-                               fwd, allow=al)
+    return G.native_backward((s, t, (K, None, radii, geom, binning, img)), dpix, antialiasing=antialiasing,
+                             debug=debug, aux=aux)
 
 
 # ------------------------------------------------------- 1. API, flag off
@@ -142,14 +83,13 @@ def test_settings_take_the_flag():
 
 def test_flag_off_is_the_plain_call():
     import gaussian_splatting_with_eye_tracking_amd._C as C
-    from test_gpu_aux_outputs import _assert_same_buffers
     sc, cam, dpix, kw, deg, ref = _reference(2, "sh")
-    s, t = _operands(sc, cam, kw, deg, False)
+    s, t = AR.operands(sc, cam, kw, deg, False)
     P, (W, H) = sc.means3D.shape[0], (cam.image_width, cam.image_height)
     K0, color0, radii0, *bufs0 = _forward(C, s, t, trailing=False)  # the 19 reference arguments
     K1, color1, radii1, *bufs1 = _forward(C, s, t)                  # ... plus antialiasing=False
     assert K0 == K1 and torch.equal(color0, color1) and torch.equal(radii0, radii1)
-    _assert_same_buffers(C, bufs0, bufs1, P, K0, W, H, radii0 > 0)
+    G.assert_same_buffers(C, bufs0, bufs1, P, K0, W, H, radii0 > 0)
     for b in (bufs0, bufs1):
         assert int(C.parse_buffers(*b, P, K0, W, H, 16)["hdr"][8]) == 0
     # the drop-in on a settings tuple of the reference's own twelve fields
@@ -170,7 +110,7 @@ def test_forward(scene, variant):
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(scene, variant)
     P, (W, H) = sc.means3D.shape[0], (cam.image_width, cam.image_height)
-    s0, t = _operands(sc, cam, kw, deg, False)
+    s0, t = AR.operands(sc, cam, kw, deg, False)
     s1 = s0._replace(antialiasing=True)
     try:
         if variant == "sh_nodrgb":
@@ -191,9 +131,9 @@ def test_forward(scene, variant):
     has_sh = "shs" in kw
     assert int(d1["hdr"][7]) == (1 if has_sh and variant != "sh_nodrgb" else 0)  # the drgb-known kernel's input
     co0, co1 = d0["conic_opacity"].cpu().numpy(), d1["conic_opacity"].cpu().numpy()
-    assert np.array_equal(_bits(co1[:, :3]), _bits(co0[:, :3]))
-    assert np.array_equal(_bits(co0[:, 3]), _bits(sc.opacities[:, 0]))
-    assert np.array_equal(_bits(co1[:, 3]), _bits(ref["o_eff"][:, 0]))  # bit-exact
+    assert np.array_equal(AR.bits(co1[:, :3]), AR.bits(co0[:, :3]))
+    assert np.array_equal(AR.bits(co0[:, 3]), AR.bits(sc.opacities[:, 0]))
+    assert np.array_equal(AR.bits(co1[:, 3]), AR.bits(ref["o_eff"][:, 0]))  # bit-exact
     l1 = G.image_l1(color1.cpu().numpy(), fwd.color)
     print(f"scene {scene} {variant}: image L1 {l1:.3e}, flag-off image differs by "
           f"{G.image_l1(color0.cpu().numpy(), fwd.color):.3e}")
@@ -207,7 +147,7 @@ def test_backward(scene, variant):
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(scene, variant)
     rg, al = _reference_grads(scene, variant)
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     try:
         if variant == "sh_nodrgb":
             C.set_thread_option("sh_drgb", 0)
@@ -215,7 +155,7 @@ def test_backward(scene, variant):
     finally:
         C.set_thread_option("sh_drgb", 1)
     grads = _backward(C, s, t, radii, geom, K, binning, img, dpix)
-    _check_grads(f"antialias_{scene}_{variant}", grads, rg, al, sc, cam, ref["fwd"])
+    AR.check_grads(f"antialias_{scene}_{variant}", grads, rg, al, sc, cam, ref["fwd"])
 
 
 def test_backward_all_at_the_floor():
@@ -226,7 +166,7 @@ def test_backward_all_at_the_floor():
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(5, "sh")
     assert np.all(ref["r32"]["ratio"] <= AR.RATIO_FLOOR)
-    s1, t = _operands(sc, cam, kw, deg, True)
+    s1, t = AR.operands(sc, cam, kw, deg, True)
     K, color, radii, geom, binning, img = _forward(C, s1, t)
     g1 = dict(zip(NAMES, _backward(C, s1, t, radii, geom, K, binning, img, dpix)))
     s0 = s1._replace(antialiasing=False)
@@ -245,7 +185,7 @@ def test_backward_all_at_the_floor():
     assert err < 1e-5, err
     rg, al = _reference_grads(5, "sh")
     assert not any(e.any() for e in rg["_coef_term"].values())
-    _check_grads("antialias_5_sh", [g1[n] for n in NAMES], rg, al, sc, cam, ref["fwd"])
+    AR.check_grads("antialias_5_sh", [g1[n] for n in NAMES], rg, al, sc, cam, ref["fwd"])
 
 
 # ------------------------------------------------------- 4. other paths
@@ -265,7 +205,7 @@ def _dropin_grads(s, t, loss_of, return_aux=False):
 def test_autograd_dropin_matches_direct_binding():
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(2, "sh")
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     K, color, radii, geom, binning, img = _forward(C, s, t)
     direct = dict(zip(NAMES, _backward(C, s, t, radii, geom, K, binning, img, dpix)))
     dp = torch.from_numpy(dpix).cuda()
@@ -279,11 +219,10 @@ def test_autograd_dropin_matches_direct_binding():
 def test_fused_training_step_matches_autograd_sequence():
     """test_gpu_training.test_fused_path_matches_autograd_path with the flag on."""
     from gaussian_splatting_with_eye_tracking_amd import training as T
-    from test_gpu_training import raw_from_scene
     sc, cam = G.scene_and_camera(5000, 160, 120, seed=9)
     s0 = G.torch_settings(cam)
     s = s0._replace(antialiasing=True)
-    raw = raw_from_scene(sc)
+    raw = G.raw_from_scene(sc)
     raw["rotation"] = raw["rotation"] * torch.linspace(0.5, 2.0, 5000, device="cuda")[:, None]  # unnormalised
     gt = torch.rand(3, 120, 160, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     out = []
@@ -313,7 +252,7 @@ def test_deterministic_mode():
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(3, "sh")
     rg, al = _reference_grads(3, "sh")
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     K, color, radii, geom, binning, img = _forward(C, s, t)
     try:
         C.set_deterministic_backward(True)
@@ -323,7 +262,7 @@ def test_deterministic_mode():
         C.set_deterministic_backward(False)
     for n, a, b in zip(NAMES, g1, g2):
         assert torch.equal(a, b), n
-    _check_grads("antialias_det_3_sh", g1, rg, al, sc, cam, ref["fwd"])
+    AR.check_grads("antialias_det_3_sh", g1, rg, al, sc, cam, ref["fwd"])
 
 
 def test_aux_maps_with_all_three_cotangents():
@@ -336,7 +275,7 @@ def test_aux_maps_with_all_three_cotangents():
     axr = AXR.reference_forward(cam, sc.means3D, ref["o_eff"], kw, bg=AR.BG)
     rg = AR.reference_backward(ref, dpix, plain=AXR.reference_backward(axr, dpix, dd, da))
     al = AR.reference_allowance(ref, dpix, plain=AXR.reference_allowance(axr, dpix, dd, da))
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     K, color, depth, alpha, radii, geom, binning, img = _forward(C, s, t, aux=True)
     K0, color0, radii0, *_ = _forward(C, s, t)
     assert K == K0 and torch.equal(color, color0) and torch.equal(radii, radii0)
@@ -344,7 +283,7 @@ def test_aux_maps_with_all_three_cotangents():
     assert G.image_l1(alpha.cpu().numpy(), axr["alpha"]) < G.IMAGE_L1_TOL
     assert G.image_l1(depth.cpu().numpy(), axr["depth"]) < G.IMAGE_L1_TOL * zmax
     grads = _backward(C, s, t, radii, geom, K, binning, img, dpix, aux=(dd, da))
-    _check_grads("antialias_aux_2_sh", grads, rg, al, sc, cam, ref["fwd"])
+    AR.check_grads("antialias_aux_2_sh", grads, rg, al, sc, cam, ref["fwd"])
     # the drop-in with return_aux
     dp, ddt, dat = (torch.from_numpy(a).cuda() for a in (dpix, dd, da))
     out, g = _dropin_grads(s, t, lambda o: (o[0] * dp).sum() + (o[2] * ddt).sum() + (o[3] * dat).sum(),
@@ -357,9 +296,9 @@ def test_aux_maps_with_all_three_cotangents():
 
 def test_c_abi_through_ctypes_matches_the_binding():
     import gaussian_splatting_with_eye_tracking_amd._C as C
-    import test_gpu_capi_ctypes as T
-    VP, I, F, p = T.VP, T.I, T.F, T._p
-    lib = T._lib()
+    import capi_helpers as T
+    VP, I, F, p = T.VP, T.I, T.F, T.ptr
+    lib = T.lib()
     lib.gs_rasterizer_forward_ex.argtypes = ([T.GsBuffer] * 3 + [I, I, I, VP, I, I, VP, VP, VP, VP, VP, F, VP, VP,
                                                                   VP, VP, VP, F, F, I, I, VP, VP, VP, VP, I, VP])
     lib.gs_rasterizer_backward_ex.argtypes = ([I, I, I, I, VP, I, I, VP, VP, VP, VP, VP, F, VP, VP, VP, VP, VP, F, F,
@@ -368,7 +307,7 @@ def test_c_abi_through_ctypes_matches_the_binding():
     lib.gs_rasterizer_forward_ex.restype = lib.gs_rasterizer_backward_ex.restype = ctypes.c_int
     sc, cam, dpix, kw, deg, ref = _reference(2, "sh")
     P, (W, H) = sc.means3D.shape[0], (cam.image_width, cam.image_height)
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     K0, col0, rad0, gb0, bb0, ib0 = _forward(C, s, t)
     g0 = _backward(C, s, t, rad0, gb0, K0, bb0, ib0, dpix)
     dpix_t = torch.from_numpy(dpix).cuda()
@@ -378,7 +317,7 @@ def test_c_abi_through_ctypes_matches_the_binding():
     with torch.cuda.stream(stream):
         colr = torch.empty((3, H, W), device="cuda")
         radii = torch.empty(P, dtype=torch.int32, device="cuda")
-        K = T._check(lib, lib.gs_rasterizer_forward_ex(
+        K = T.check(lib, lib.gs_rasterizer_forward_ex(
             bufs.buf("geom"), bufs.buf("binning"), bufs.buf("image"), P, 3, 16, p(s.bg), W, H, p(t["means3D"]),
             p(t["shs"]), VP(0), p(t["opacities"]), p(t["scales"]), F(1.0), p(t["rotations"]), VP(0),
             p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx), F(s.tanfovy), 0, 1, p(colr), p(radii),
@@ -386,7 +325,7 @@ def test_c_abi_through_ctypes_matches_the_binding():
         outs = [torch.empty(shape, device="cuda") for shape in ((P, 3), (P, 1), (P, 3), (P, 3), (P, 6), (P, 16, 3),
                                                                 (P, 3), (P, 4))]
         m2, op, cl, m3, cv, shg, scl, rot = outs
-        T._check(lib, lib.gs_rasterizer_backward_ex(
+        T.check(lib, lib.gs_rasterizer_backward_ex(
             P, 3, 16, K, p(s.bg), W, H, p(t["means3D"]), p(t["shs"]), VP(0), p(t["opacities"]), p(t["scales"]),
             F(1.0), p(t["rotations"]), VP(0), p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx),
             F(s.tanfovy), p(radii), p(bufs.t["geom"]), p(bufs.t["binning"]), p(bufs.t["image"]), p(dpix_t), VP(0),
@@ -413,7 +352,7 @@ def test_c_abi_through_ctypes_matches_the_binding():
 def test_amr_rasterizer_refuses_the_flag():
     from diff_gaussian_rasterization_amr import GaussianRasterizer
     sc, cam, dpix, kw, deg, ref = _reference(1, "sh")
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     ops = dict(means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], shs=t["shs"],
                scales=t["scales"], rotations=t["rotations"])
     with pytest.raises(NotImplementedError, match="antialias"):
@@ -427,16 +366,15 @@ def test_view_exchange_refuses_the_flag():
     import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
     from gaussian_splatting_with_eye_tracking_amd import training as T
-    from test_gpu_training import raw_from_scene
     sc, cam, dpix, kw, deg, ref = _reference(1, "sh")
-    s, t = _operands(sc, cam, kw, deg, True)
+    s, t = AR.operands(sc, cam, kw, deg, True)
     fwd = _forward(C, s, t)
     dp = torch.from_numpy(dpix).cuda()
     with pytest.raises(NotImplementedError, match="antialias"):
         DP.exchange_view_grads(s, fwd, dp, t["means3D"], t["shs"], t["scales"], t["rotations"])
     with pytest.raises(NotImplementedError, match="antialias"):
         DP.view_record(s, fwd[2], fwd[3], fwd[0], fwd[4], fwd[5], dp)
-    m = T.FlatGaussianModel(raw_from_scene(sc), 3, spatial_lr_scale=5.0)
+    m = T.FlatGaussianModel(G.raw_from_scene(sc), 3, spatial_lr_scale=5.0)
     gt = torch.rand(3, cam.image_height, cam.image_width, device="cuda")
     with pytest.raises(NotImplementedError, match="antialias"):
         T.render_and_backward_views(m, s, gt, 0.2, stats=False)
@@ -449,7 +387,7 @@ def test_backward_flag_must_be_the_forwards(forward_flag):
     error under debug."""
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam, dpix, kw, deg, ref = _reference(1, "sh")
-    s, t = _operands(sc, cam, kw, deg, forward_flag)
+    s, t = AR.operands(sc, cam, kw, deg, forward_flag)
     K, color, radii, geom, binning, img = _forward(C, s, t)
     bad = _backward(C, s, t, radii, geom, K, binning, img, dpix, antialiasing=not forward_flag)
     vis = radii > 0

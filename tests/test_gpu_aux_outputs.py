@@ -29,8 +29,7 @@ CASES = [
     ("dense_20k_128", 20000, 128, 128, 11),       # lists longer than one LDS batch, large-tile sort path
 ]
 BG = (0.1, 0.2, 0.3)
-NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-         "dL_drotations"]
+NAMES = AR.NAMES
 
 
 def _colors(P, seed):
@@ -48,13 +47,6 @@ def _reference(P, W, H, seed, variant):
     return sc, cam, AR.reference_forward(cam, sc.means3D, sc.opacities, kw, bg=BG)
 
 
-def _cotangents(W, H, seed):
-    dpix = S.make_cotangent(H, W, seed + 1)
-    dd = np.ascontiguousarray(S.make_cotangent(H, W, seed + 2)[0:1])
-    da = np.ascontiguousarray(S.make_cotangent(H, W, seed + 3)[0:1])
-    return dpix, dd, da
-
-
 def _operands(sc, cam, variant, seed, bg=BG):
     s = G.torch_settings(cam, bg=bg)
     t = G.scene_tensors(sc)
@@ -64,61 +56,23 @@ def _operands(sc, cam, variant, seed, bg=BG):
     return s, t, sh, col
 
 
+def _full(t, sh, col):
+    return dict(t, shs=sh, colors_precomp=col, cov3D_precomp=torch.Tensor([]))
+
+
 def _forward(C, fn, s, t, sh, col):
-    e = torch.Tensor([])
-    out = fn(s.bg, t["means3D"], col, t["opacities"], t["scales"], t["rotations"], s.scale_modifier, e,
-             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
-             s.campos, s.prefiltered, s.debug)
-    torch.cuda.synchronize()
-    return out
+    return G.native_forward(None, None, settings=s, tensors=_full(t, sh, col), aux=fn is C.rasterize_gaussians_aux,
+                            trailing=False)[2]
 
 
 def _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da):
-    e = torch.Tensor([])
-    W, H = s.image_width, s.image_height
-    cu = lambda a: e.cuda() if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
-    dp = torch.zeros((3, H, W), device="cuda") if dpix is None else cu(dpix)
-    g = C.rasterize_gaussians_backward_aux(s.bg, t["means3D"], radii, col, t["scales"], t["rotations"],
-                                           s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dp,
-                                           cu(dd), cu(da), sh, s.sh_degree, s.campos, geom, K, binning, img, False)
-    torch.cuda.synchronize()
-    return g
+    dp = torch.zeros((3, s.image_height, s.image_width), device="cuda") if dpix is None else dpix
+    return G.native_backward((s, _full(t, sh, col), (K, None, radii, geom, binning, img)), dp, aux=(dd, da),
+                             trailing=False)
 
 
 def _backward_plain(C, s, t, sh, col, radii, geom, K, binning, img, dpix):
-    e = torch.Tensor([])
-    g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, col, t["scales"], t["rotations"], s.scale_modifier,
-                                       e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                       torch.from_numpy(dpix).cuda(), sh, s.sh_degree, s.campos, geom, K, binning, img,
-                                       False)
-    torch.cuda.synchronize()
-    return g
-
-
-def _assert_same_buffers(C, a, b, P, K, W, H, vis):
-    """Every field of the two forwards' geometry / image / binning buffers
-    (per-Gaussian records of the visible Gaussians: the culled ones' are never
-    written; header: the words a forward defines whatever the binning
-    buffer's capacity)."""
-    da = C.parse_buffers(*a, P, K, W, H, 16)
-    db = C.parse_buffers(*b, P, K, W, H, 16)
-    assert set(da) == set(db)
-    per_gaussian = {"depths", "means2D", "conic_opacity", "rgb", "clamped_bits", "cov3D"}
-    # AMR / scratch words, and the geometry buffer's own radii slot: the
-    # binding hands the forward its radii tensor (compared by the caller), so
-    # the slot is never written
-    skip = {"hdr", "levels", "levels_last", "levels_current", "pv", "tile_count", "radii"}
-    for k in da:
-        if k in skip:
-            continue
-        if k in per_gaussian:
-            if k != "cov3D":  # (written on request only)
-                assert torch.equal(da[k][vis], db[k][vis]), k
-        else:
-            assert torch.equal(da[k], db[k]), k
-    for w in (0, 2, 3, 7):  # K, the tile statistics, the drgb flag
-        assert int(da["hdr"][w]) == int(db["hdr"][w]), w
-    assert (int(da["hdr"][6]) != 0) == (int(db["hdr"][6]) != 0)  # hit codes left (compared above)
+    return G.native_backward((s, _full(t, sh, col), (K, None, radii, geom, binning, img)), dpix, trailing=False)
 
 
 # --------------------------------------------------------------- 1. forward
@@ -134,7 +88,7 @@ def test_forward_parity(name, P, W, H, seed):
     assert depth.dtype == torch.float32 and alpha.dtype == torch.float32
     assert torch.equal(color, color0) and torch.equal(radii, radii0)
     assert geom.numel() == geom0.numel() and img.numel() == img0.numel()
-    _assert_same_buffers(C, (geom, binning, img), (geom0, bin0, img0), P, K, W, H, radii0 > 0)
+    G.assert_same_buffers(C, (geom, binning, img), (geom0, bin0, img0), P, K, W, H, radii0 > 0)
     zmax = float(ref["fwd"].depths[ref["fwd"].radii > 0].max())
     assert zmax < 20.0
     l1a = G.image_l1(alpha.cpu().numpy(), ref["alpha"])
@@ -148,22 +102,6 @@ def test_forward_parity(name, P, W, H, seed):
 
 
 # -------------------------------------------------------------- 2. backward
-def _check_against_reference(case, grads, ref, sc, cam, dpix, dd, da):
-    rg = AR.reference_backward(ref, dpix, dd, da)
-    al = AR.reference_allowance(ref, dpix, dd, da)
-    for n, g in zip(NAMES, grads):
-        gg = g.cpu().numpy()
-        assert np.all(np.isfinite(gg)), n
-        if n not in rg:  # (no SH input: an empty gradient)
-            assert n == "dL_dsh" and gg.size == 0, n
-            continue
-        assert gg.shape == rg[n].shape, n
-        err = G.rel_err(gg, rg[n])
-        print(f"{case} {n}: rel err {err:.3e}")
-        assert err < G.GRAD_REL_TOL, (n, err)
-    G.assert_grads_elementwise(case, NAMES, grads, rg, sc, cam, ref["fwd"], allow=al)
-
-
 @pytest.mark.parametrize("name,P,W,H,seed", CASES)
 @pytest.mark.parametrize("variant", ["sh", "colors_precomp"])
 def test_backward_parity(name, P, W, H, seed, variant):
@@ -171,9 +109,9 @@ def test_backward_parity(name, P, W, H, seed, variant):
     sc, cam, ref = _reference(P, W, H, seed, variant)
     s, t, sh, col = _operands(sc, cam, variant, seed)
     K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
-    dpix, dd, da = _cotangents(W, H, seed)
+    dpix, dd, da = AR.cotangents(W, H, seed)
     grads = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
-    _check_against_reference(f"aux_backward_{name}_{variant}", grads, ref, sc, cam, dpix, dd, da)
+    AR.check_against_reference(f"aux_backward_{name}_{variant}", grads, ref, sc, cam, dpix, dd, da)
 
 
 # ------------------------------------------------- 3. linearity and absence
@@ -184,10 +122,10 @@ def test_single_aux_cotangent(name, P, W, H, seed, which):
     sc, cam, ref = _reference(P, W, H, seed, "sh")
     s, t, sh, col = _operands(sc, cam, "sh", seed)
     K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
-    _, dd, da = _cotangents(W, H, seed)
+    _, dd, da = AR.cotangents(W, H, seed)
     dd, da = (dd, None) if which == "depth" else (None, da)
     grads = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, None, dd, da)
-    _check_against_reference(f"aux_only_{which}_{name}", grads, ref, sc, cam, None, dd, da)
+    AR.check_against_reference(f"aux_only_{which}_{name}", grads, ref, sc, cam, None, dd, da)
     if which == "alpha":  # no depth cotangent: no colour and no SH gradient at all
         assert float(grads[1].abs().max()) == 0.0 and float(grads[5].abs().max()) == 0.0
 
@@ -237,7 +175,7 @@ def test_autograd_dropin_matches_direct_binding():
     color, radii, depth, alpha = ras(return_aux=True, **kw)
     assert torch.equal(color, plain[0]) and torch.equal(radii, plain[1])
     assert depth.requires_grad and alpha.requires_grad and not radii.requires_grad
-    dpix, dd, _ = _cotangents(W, H, seed)
+    dpix, dd, _ = AR.cotangents(W, H, seed)
     dpix_t, wd = torch.from_numpy(dpix).cuda(), torch.from_numpy(dd).cuda()
     loss = (depth / (alpha + 1e-6) * wd).sum() + (color * dpix_t).sum()
     loss.backward()
@@ -324,7 +262,7 @@ def test_all_culled():
     assert K == 0 and torch.all(radii == 0)
     np.testing.assert_allclose(color.cpu().numpy()[:, 0, 0], [0.5, 0.25, 0.125])
     assert torch.all(depth == 0) and torch.all(alpha == 0)
-    dpix, dd, da = _cotangents(64, 48, 0)
+    dpix, dd, da = AR.cotangents(64, 48, 0)
     for g in _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da):
         assert torch.all(g == 0)
 
@@ -334,7 +272,7 @@ def test_second_aux_backward_and_plain_backward_after_aux_forward():
     name, P, W, H, seed = CASES[1]
     sc, cam = G.scene_and_camera(P, W, H, seed)
     s, t, sh, col = _operands(sc, cam, "sh", seed)
-    dpix, dd, da = _cotangents(W, H, seed)
+    dpix, dd, da = AR.cotangents(W, H, seed)
     K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
     g1 = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
     g2 = _backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
@@ -372,7 +310,7 @@ def test_deterministic_mode_refuses_aux_cotangents():
         # the direct binding under the native flag refuses too
         s2, t2, sh, col = _operands(sc, cam, "sh", seed)
         K, color, depth, alpha, radii, geom, binning, img = _forward(C, C.rasterize_gaussians_aux, s2, t2, sh, col)
-        dpix, dd, da = _cotangents(W, H, seed)
+        dpix, dd, da = AR.cotangents(W, H, seed)
         with pytest.raises(RuntimeError, match="deterministic"):
             _backward_aux(C, s2, t2, sh, col, radii, geom, K, binning, img, dpix, dd, da)
     finally:
@@ -385,9 +323,9 @@ def test_deterministic_mode_refuses_aux_cotangents():
 # ------------------------------------------------------------------ 6. C ABI
 def test_c_abi_through_ctypes_matches_the_binding():
     import gaussian_splatting_with_eye_tracking_amd._C as C
-    import test_gpu_capi_ctypes as T
+    import capi_helpers as T
     VP, I, F = T.VP, T.I, T.F
-    lib = T._lib()
+    lib = T.lib()
     fwd = [T.GsBuffer] * 3 + [I, I, I, VP, I, I, VP, VP, VP, VP, VP, F, VP, VP, VP, VP, VP, F, F, I]
     lib.gs_rasterizer_forward_aux.argtypes = fwd + [VP, VP, VP, VP, I, VP]
     lib.gs_rasterizer_backward_aux.argtypes = ([I, I, I, I, VP, I, I, VP, VP, VP, VP, F, VP, VP, VP, VP, VP, F, F, VP,
@@ -396,20 +334,20 @@ def test_c_abi_through_ctypes_matches_the_binding():
     name, P, W, H, seed = CASES[1]
     sc, cam = G.scene_and_camera(P, W, H, seed)
     s, t, sh, col = _operands(sc, cam, "sh", seed)
-    dpix, dd, da = _cotangents(W, H, seed)
+    dpix, dd, da = AR.cotangents(W, H, seed)
     K0, col0, dep0, alp0, rad0, gb0, bb0, ib0 = _forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
     g0 = _backward_aux(C, s, t, sh, col, rad0, gb0, K0, bb0, ib0, dpix, dd, da)
     dpix_t, dd_t, da_t = (torch.from_numpy(a).cuda() for a in (dpix, dd, da))
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
     bufs = T.Buffers(t["means3D"].device)
-    p = T._p
+    p = T.ptr
     with torch.cuda.stream(stream):
         colr = torch.empty((3, H, W), device="cuda")
         dep = torch.empty((1, H, W), device="cuda")
         alp = torch.empty((1, H, W), device="cuda")
         radii = torch.empty(P, dtype=torch.int32, device="cuda")
-        K = T._check(lib, lib.gs_rasterizer_forward_aux(
+        K = T.check(lib, lib.gs_rasterizer_forward_aux(
             bufs.buf("geom"), bufs.buf("binning"), bufs.buf("image"), P, 3, 16, p(s.bg), W, H, p(t["means3D"]),
             p(t["shs"]), VP(0), p(t["opacities"]), p(t["scales"]), F(1.0), p(t["rotations"]), VP(0),
             p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx), F(s.tanfovy), 0, p(colr), p(radii), p(dep),
@@ -417,7 +355,7 @@ def test_c_abi_through_ctypes_matches_the_binding():
         outs = [torch.empty(shape, device="cuda") for shape in ((P, 3), (P, 1), (P, 3), (P, 3), (P, 6), (P, 16, 3),
                                                                 (P, 3), (P, 4))]
         m2, op, cl, m3, cv, shg, scl, rot = outs
-        T._check(lib, lib.gs_rasterizer_backward_aux(
+        T.check(lib, lib.gs_rasterizer_backward_aux(
             P, 3, 16, K, p(s.bg), W, H, p(t["means3D"]), p(t["shs"]), VP(0), p(t["scales"]), F(1.0),
             p(t["rotations"]), VP(0), p(s.viewmatrix), p(s.projmatrix), p(s.campos), F(s.tanfovx), F(s.tanfovy),
             p(radii), p(bufs.t["geom"]), p(bufs.t["binning"]), p(bufs.t["image"]), p(dpix_t), p(dd_t), p(da_t), p(m2),

@@ -36,32 +36,21 @@ def _adversarial_scene(P, W, H, seed):
     return sc, cam
 
 
-def _forward(sc, cam, fwd_variant):
+def _forward(sc, cam):
     import gaussian_splatting_with_eye_tracking_amd._C as C
-    C.set_tuning("fwd_variant", fwd_variant)
-    s = G.torch_settings(cam)
-    t = G.scene_tensors(sc)
-    e = torch.Tensor([])
-    out = C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e,
-                                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-                                t["shs"], 3, s.campos, False, False)
+    s, t, out = G.native_forward(sc, cam)
     K, color, radii, geom, binning, img = out
     bufs = C.parse_buffers(geom, binning, img, sc.P, K, s.image_width, s.image_height, 16)
     torch.cuda.synchronize()
     return s, t, out, {k: bufs[k].clone() for k in ("accum_alpha", "n_contrib", "max_contrib")}
 
 
-def _backward(s, t, out, dpix, bwd_variant):
+def _backward(s, t, out, dpix):
     """Returns the 8 reference gradients and the blend kernel's per-Gaussian
     sums grad_accum[P][9] (dL/dcolor 3, dL/dmean2D 2, dL/dconic 3, dL/dopacity)."""
     import gaussian_splatting_with_eye_tracking_amd._C as C
-    C.set_tuning("bwd_variant", bwd_variant)
     K, color, radii, geom, binning, img = out
-    e = torch.Tensor([])
-    g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                       s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], 3,
-                                       s.campos, geom, K, binning, img, False)
-    torch.cuda.synchronize()
+    g = G.native_backward((s, t, out), dpix)
     P = t["means3D"].shape[0]
     acc = C.parse_buffers(geom, binning, img, P, K, s.image_width, s.image_height, 16)["grad_accum"]
     return [x.cpu().numpy() for x in g], acc[:, :9].cpu().numpy()
@@ -76,21 +65,15 @@ def test_cull_is_exact(P, W, H, seed, variant):
     of those sums; on this scene the Jacobians of the huge thin splats
     amplify the run-to-run atomic noise of dL/dconic to ~1e-3, cull or not,
     so they are compared on the default scene below instead.)"""
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     sc, cam = _adversarial_scene(P, W, H, seed)
     dpix = torch.from_numpy(S.make_cotangent(H, W, seed + 1)).cuda()
     res = {}
-    try:
-        for cull in (0, 1):
-            C.set_tuning("cull", cull)
-            s, t, out, bufs = _forward(sc, cam, variant)
-            grads, acc = _backward(s, t, out, dpix, variant)
-            res[cull] = (out[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in bufs.items()}, grads, acc)
-    finally:
-        C.set_tuning("cull", 1)
-        C.set_tuning("fwd_variant", -1)
-        C.set_tuning("bwd_variant", -1)
+    for cull in (0, 1):
+        with G.tuning(cull=cull, fwd_variant=variant, bwd_variant=variant):
+            s, t, out, bufs = _forward(sc, cam)
+            grads, acc = _backward(s, t, out, dpix)
+        res[cull] = (out[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in bufs.items()}, grads, acc)
     np.testing.assert_array_equal(res[0][0], res[1][0])  # image, bit-exact
     for k in res[0][1]:
         np.testing.assert_array_equal(res[0][1][k], res[1][1][k], err_msg=k)
@@ -105,39 +88,31 @@ def test_cull_is_exact(P, W, H, seed, variant):
 
 def test_cull_is_exact_default_scene_gradients():
     """On the benchmark's scene distribution every gradient agrees to 1e-5."""
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     sc, cam = G.scene_and_camera(20000, 320, 200, 3)
     dpix = torch.from_numpy(S.make_cotangent(200, 320, 4)).cuda()
     res = {}
-    try:
-        for cull in (0, 1):
-            C.set_tuning("cull", cull)
-            s, t, out, bufs = _forward(sc, cam, 1)
-            res[cull] = (out[1].cpu().numpy(), _backward(s, t, out, dpix, 1)[0])
-    finally:
-        C.set_tuning("cull", 1)
+    for cull in (0, 1):
+        with G.tuning(cull=cull, fwd_variant=1, bwd_variant=1):
+            s, t, out, bufs = _forward(sc, cam)
+            res[cull] = (out[1].cpu().numpy(), _backward(s, t, out, dpix)[0])
     np.testing.assert_array_equal(res[0][0], res[1][0])
     for a, b in zip(res[0][1], res[1][1]):
         assert G.rel_err(b, a) < 1e-5
 
 
 def test_cull_is_exact_amr_render_once():
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from diff_gaussian_rasterization_amr import GaussianRasterizer
     sc, cam = _adversarial_scene(12000, 288, 160, 4)
     s = G.torch_settings(cam, amr=True)
     t = G.scene_tensors(sc)
     imgs = {}
-    try:
-        for cull in (0, 1):
-            C.set_tuning("cull", cull)
+    for cull in (0, 1):
+        with G.tuning(cull=cull):
             color, *_ = GaussianRasterizer(s)(
                 means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"],
                 shs=t["shs"], scales=t["scales"], rotations=t["rotations"], foveaStep=-2, interpolate_image=True)
             imgs[cull] = color.cpu().numpy()
-    finally:
-        C.set_tuning("cull", 1)
     np.testing.assert_array_equal(imgs[0], imgs[1])
 
 
@@ -151,18 +126,14 @@ def test_default_backward_matches_fallback(P, W, H, seed, fwd):
     the adversarial scene (huge thin splats, near-degenerate conics), after
     the default forward (hit codes) and the fallback forward (geometric
     cull): the blend sums agree to float-atomic ordering noise."""
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     sc, cam = _adversarial_scene(P, W, H, seed)
     dpix = torch.from_numpy(S.make_cotangent(H, W, seed + 1)).cuda()
     res = {}
-    try:
-        for v in (0, 1, 2):
-            s, t, out, _bufs = _forward(sc, cam, fwd)
-            res[v] = _backward(s, t, out, dpix, v)
-    finally:
-        C.set_tuning("fwd_variant", -1)
-        C.set_tuning("bwd_variant", -1)
+    for v in (0, 1, 2):
+        with G.tuning(fwd_variant=fwd, bwd_variant=v):
+            s, t, out, _bufs = _forward(sc, cam)
+            res[v] = _backward(s, t, out, dpix)
     for v in (1, 2):
         for i in range(3):  # dL_dmeans2D, dL_dcolors, dL_dopacity
             assert G.rel_err(res[v][0][i], res[0][0][i]) < 5e-6, (v, i)
@@ -186,13 +157,11 @@ def test_default_forward_bit_identical_to_fallback(P, W, H, seed, adv):
         cam = S.make_camera(W, H)
         sc = S.make_scene(P, cam, seed=seed)
     res = {}
-    try:
-        for v in (0, 1):
-            s, t, out, bufs = _forward(sc, cam, v)
-            hdr = C.parse_buffers(out[3], out[4], out[5], P, int(out[0]), W, H, 16)["hdr"]
-            res[v] = (out[1].cpu().numpy(), {k: b.cpu().numpy() for k, b in bufs.items()}, int(hdr[6].item()))
-    finally:
-        C.set_tuning("fwd_variant", -1)
+    for v in (0, 1):
+        with G.tuning(fwd_variant=v):
+            s, t, out, bufs = _forward(sc, cam)
+        hdr = C.parse_buffers(out[3], out[4], out[5], P, int(out[0]), W, H, 16)["hdr"]
+        res[v] = (out[1].cpu().numpy(), {k: b.cpu().numpy() for k, b in bufs.items()}, int(hdr[6].item()))
     np.testing.assert_array_equal(res[1][0], res[0][0])
     for k in res[1][1]:
         np.testing.assert_array_equal(res[1][1][k], res[0][1][k], err_msg=k)

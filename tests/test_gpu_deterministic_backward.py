@@ -23,14 +23,14 @@ import numpy as np
 import pytest
 
 import gs_helpers as G
-import test_gpu_parity as TP
+from capi_helpers import F, I, VP, ptr as _p
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
          "dL_drotations"]
-SHAPES = {c[0]: c[1:] for c in TP.CASES}
+SHAPES = {c[0]: c[1:] for c in G.PARITY_CASES}
 THREE = ["g1_64_32x32", "ragged_3k_250x130", "dense_20k_128"]
 BG = (0.2, 0.1, 0.05)
 
@@ -50,7 +50,7 @@ def _case(name, variant="sh"):
     if variant == "colors_precomp":
         colors = np.random.default_rng(seed + 5).uniform(0, 1, (P, 3)).astype(np.float32)
     if variant == "cov3D_precomp":
-        _, r0, _ = TP._oracle_forward(sc, cam)
+        _, r0, _ = G.oracle_forward(sc, cam)
         cov = r0.cov3D.copy()
         cov[r0.radii <= 0] = np.array([1e-4, 0, 0, 1e-4, 0, 1e-4], np.float32)
     return dict(P=P, W=W, H=H, seed=seed, sc=sc, cam=cam, colors=colors, cov=cov,
@@ -62,37 +62,19 @@ def _oracle(name, variant="sh"):
     """The oracle's gradients and allowance of one case (computed once)."""
     import oracle as O
     c = _case(name, variant)
-    os_, ref, kw = TP._oracle_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
+    os_, ref, kw = G.oracle_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
     rg = O.backward(os_, ref, c["sc"].means3D, c["dpix"], **kw)
     al, ties = O.grad_allowance(os_, ref, c["sc"].means3D, c["dpix"], parts=True, **kw)
     return ref, rg, al, ties
 
 
 def _forward(c):
-    return TP._gpu_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
+    return G.native_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
 
 
 def _backward(c, fwd, det, lean=False):
     """The raw backward binding on one forward, with the native flag at `det`."""
-    C = _C()
-    s, t, (K, color, radii, geom, binning, img) = fwd
-    e = torch.Tensor([])
-    sh = t["shs"] if c["colors"] is None else e
-    colt = e if c["colors"] is None else torch.from_numpy(c["colors"]).cuda()
-    scales = t["scales"] if c["cov"] is None else e
-    rots = t["rotations"] if c["cov"] is None else e
-    covt = e if c["cov"] is None else torch.from_numpy(c["cov"]).cuda()
-    fn = C.rasterize_gaussians_backward_lean if lean else C.rasterize_gaussians_backward
-    prev = C.get_deterministic_backward()
-    C.set_deterministic_backward(det)
-    try:
-        g = fn(s.bg, t["means3D"], radii, colt, scales, rots, s.scale_modifier, covt, s.viewmatrix, s.projmatrix,
-               s.tanfovx, s.tanfovy, torch.from_numpy(c["dpix"]).cuda(), sh, s.sh_degree, s.campos, geom, K, binning,
-               img, False)
-        torch.cuda.synchronize()
-    finally:
-        C.set_deterministic_backward(prev)
-    return list(g)
+    return G.native_backward(fwd, c["dpix"], det=det, lean=lean)
 
 
 def _assert_same_bits(a, b, what=""):
@@ -154,7 +136,6 @@ def test_bit_reproducible(name):
 @pytest.mark.parametrize("name", THREE)
 def test_independent_of_launch_order_and_tunings(name):
     import gaussian_splatting_with_eye_tracking_amd as pkg
-    C = _C()
     c = _case(name)
     base = _backward(c, _forward(c), True)
     # the work buckets zeroed: every block takes the identity tile order
@@ -166,19 +147,13 @@ def test_independent_of_launch_order_and_tunings(name):
     f = _forward(c)
     f[2][5][off:off + 1024].zero_()
     _assert_same_bits(base, _backward(c, f, True), "zeroed work buckets")
-    v0, c0 = C.get_tuning("bwd_variant"), C.get_tuning("cull")
-    try:
-        C.set_tuning("bwd_variant", 0)
+    with G.tuning(bwd_variant=0):
         _assert_same_bits(base, _backward(c, _forward(c), True), "bwd_variant 0")
-        C.set_tuning("bwd_variant", v0)
-        C.set_tuning("cull", 0)
+    with G.tuning(cull=0):
         r0 = _backward(c, _forward(c), True)
-        C.set_tuning("cull", 1)
+    with G.tuning(cull=1):
         r1 = _backward(c, _forward(c), True)
-        _assert_same_bits(r0, r1, "cull 0 / 1")
-    finally:
-        C.set_tuning("bwd_variant", v0)
-        C.set_tuning("cull", c0)
+    _assert_same_bits(r0, r1, "cull 0 / 1")
 
 
 # ------------------------------------------ 4. close to the default path
@@ -199,6 +174,32 @@ def test_close_to_default_path(name):
             assert y.numel() == 0, n
         else:
             assert torch.equal(x, y), n
+
+
+@pytest.mark.parametrize("variant", ["sh", "colors_precomp"])
+@pytest.mark.parametrize("name", ["g1_64_32x32", "ragged_3k_250x130"])
+def test_base_backward_bindings_agree(name, variant):
+    """The four base backward bindings reach the library through one call: on
+    one forward, under the deterministic flag (bit-reproducible), _lean, and
+    _aux / _aux_lean with both map cotangents empty, return
+    rasterize_gaussians_backward's bits -- the lean forms with dL_dcolors /
+    dL_dcov3D empty exactly when that input was -- and a map cotangent under
+    the flag is still refused."""
+    c = _case(name, variant)
+    fwd = _forward(c)
+    plain = G.native_backward(fwd, c["dpix"], det=True)
+    given = {"dL_dcolors": c["colors"] is not None, "dL_dcov3D": c["cov"] is not None}
+    for kw in (dict(lean=True), dict(aux=(None, None)), dict(aux=(None, None), lean=True)):
+        got = G.native_backward(fwd, c["dpix"], det=True, **kw)
+        for n, x, y in zip(NAMES, plain, got):
+            if kw.get("lean") and not given.get(n, True):
+                assert y.numel() == 0, (kw, n)
+            else:  # (the plain form's, so not empty where the input was given)
+                assert x.shape == y.shape and torch.equal(x, y), (kw, n)
+    dalpha = np.ones((1, c["H"], c["W"]), np.float32)
+    for lean in (False, True):
+        with pytest.raises(RuntimeError, match="no deterministic aux backward is built"):
+            G.native_backward(fwd, c["dpix"], det=True, aux=(None, dalpha), lean=lean)
 
 
 # --------------------------------------------------------- 5. autograd
@@ -344,9 +345,6 @@ def test_view_records_bit_identical():
 
 
 # ---------------------------------------------------- 7. the C ABI
-VP, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-
-
 def _lib():
     import gaussian_splatting_with_eye_tracking_amd as pkg
     lib = ctypes.CDLL(os.path.join(os.path.dirname(pkg.__file__), "libgsplat_amd.so"))
@@ -358,10 +356,6 @@ def _lib():
     lib.gs_backward_deterministic_scratch_bytes.restype = ctypes.c_size_t
     lib.gs_last_error.restype = ctypes.c_char_p
     return lib
-
-
-def _p(t):
-    return VP(t.data_ptr()) if t is not None and t.numel() else VP(0)
 
 
 def test_c_abi_with_nan_filled_scratch_and_short_scratch():
@@ -448,7 +442,6 @@ def test_training_runs_bit_identical():
     the same state agree bit for bit in every parameter, gradient and Adam
     moment after each of three iterations."""
     from gaussian_splatting_with_eye_tracking_amd import set_deterministic, training as T
-    from test_gpu_training import raw_from_scene
     P, W, H, seed = SHAPES["cfg1_10k_256"]
     sc, cam = G.scene_and_camera(P, W, H, seed)
     s = G.torch_settings(cam)
@@ -457,7 +450,7 @@ def test_training_runs_bit_identical():
 
     def run():
         torch.manual_seed(0)
-        m = T.FlatGaussianModel(raw_from_scene(sc), 3, spatial_lr_scale=5.0, opt=opt)
+        m = T.FlatGaussianModel(G.raw_from_scene(sc), 3, spatial_lr_scale=5.0, opt=opt)
         m.active_sh_degree = 3
         snaps = []
         for it in range(1, 4):

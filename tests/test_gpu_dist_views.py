@@ -44,13 +44,6 @@ def _setup(rank):
     return G, s, t, dpix
 
 
-def _fwd(C, s, t):
-    e = torch.Tensor([])
-    return C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e,
-                                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-                                 t["shs"], 3, s.campos, False, False)
-
-
 def _worker(rank, world, port, q):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -58,10 +51,9 @@ def _worker(rank, world, port, q):
     try:
         import sys
         sys.path.insert(0, ROOT)
-        import gaussian_splatting_with_eye_tracking_amd._C as C
         from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
         G, s, t, dpix = _setup(rank)
-        fwd = _fwd(C, s, t)
+        fwd = G.native_forward(None, None, settings=s, tensors=t)[2]
         # one record (the blend backward's float atomics add in a run-dependent
         # order), exchanged with one gather and with 3 asynchronous chunks
         rec = DP.view_record(s, fwd[2], fwd[3], fwd[0], fwd[4], fwd[5], dpix)
@@ -124,16 +116,10 @@ def test_two_rank_view_exchange():
         np.testing.assert_array_equal(outs[1]["stacked"][i], outs[1]["pipelined"][i])
         np.testing.assert_array_equal(outs[0]["pipelined"][i], outs[1]["pipelined"][i])
     # == sum over the two views of the reference-API backward
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     want = None
     for rank in range(world):
         G, s, t, dpix = _setup(rank)
-        fwd = _fwd(C, s, t)
-        K, color, radii, geom, binning, img = fwd
-        e = torch.Tensor([])
-        g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                           s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], 3,
-                                           s.campos, geom, K, binning, img, False)
+        g = G.native_backward(G.native_forward(None, None, settings=s, tensors=t), dpix)
         per = [g[3], g[5], g[2], g[6], g[7]]
         want = [x.double().cpu().numpy() for x in per] if want is None else \
             [a + x.double().cpu().numpy() for a, x in zip(want, per)]

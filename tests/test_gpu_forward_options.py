@@ -15,7 +15,7 @@ import re
 import pytest
 
 import gs_helpers as G
-from test_gpu_capi_ctypes import GsBuffer, _lib
+from capi_helpers import GsBuffer, lib as _lib
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -37,9 +37,8 @@ def test_forward_options_are_consumed_once():
     drgb = _hdr_word("kHdrDrgb")
 
     def forward(colors=e):
-        K, _c, _r, gb, bb, ib = C.rasterize_gaussians(
-            s.bg, t["means3D"], colors, t["opacities"], t["scales"], t["rotations"], 1.0, e, s.viewmatrix,
-            s.projmatrix, s.tanfovx, s.tanfovy, H, W, e if colors.numel() else t["shs"], 3, s.campos, False, False)
+        K, _c, _r, gb, bb, ib = G.native_forward(sc, cam, colors if colors.numel() else None, settings=s,
+                                                 tensors=t)[2]
         return C.parse_buffers(gb, bb, ib, P, K, W, H, 16)
 
     try:

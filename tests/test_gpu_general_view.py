@@ -50,11 +50,6 @@ def _C():
     return C
 
 
-def _TP():
-    import test_gpu_parity as TP
-    return TP
-
-
 # ------------------------------------------------------------ shared references
 @functools.lru_cache(maxsize=None)
 def _case(name, variant="sh"):
@@ -65,7 +60,7 @@ def _case(name, variant="sh"):
     if variant == "colors_precomp":
         colors = np.random.default_rng(seed + 5).uniform(0, 1, (P, 3)).astype(np.float32)
     if variant == "cov3D_precomp":
-        _, r0, _ = _TP()._oracle_forward(sc, cam)
+        _, r0, _ = G.oracle_forward(sc, cam)
         cov = r0.cov3D.copy()
         cov[r0.radii <= 0] = np.array([1e-4, 0, 0, 1e-4, 0, 1e-4], np.float32)  # (never computed: a valid one)
     return dict(P=P, W=W, H=H, seed=seed, sc=sc, cam=cam, colors=colors, cov=cov, dpix=dpix)
@@ -76,7 +71,7 @@ def _oracle(name, variant="sh"):
     """The oracle's forward, gradients, allowance and census of one case
     (computed once, left unchanged)."""
     c = _case(name, variant)
-    os_, ref, kw = _TP()._oracle_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
+    os_, ref, kw = G.oracle_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=BG)
     rg = O.backward(os_, ref, c["sc"].means3D, c["dpix"], **kw)
     al, ties = O.grad_allowance(os_, ref, c["sc"].means3D, c["dpix"], parts=True, **kw)
     census = G.general_case_census(c["sc"], c["cam"], ref, rg)
@@ -91,12 +86,11 @@ def _covered(name, variant="sh"):
 
 
 def _forward(c, bg=BG):
-    return _TP()._gpu_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=bg)
+    return G.native_forward(c["sc"], c["cam"], c["colors"], c["cov"], bg=bg)
 
 
 def _backward(c, fwd, det=False, lean=False):
-    import test_gpu_deterministic_backward as TD
-    return TD._backward(c, fwd, det, lean=lean)
+    return G.native_backward(fwd, c["dpix"], det=det, lean=lean)
 
 
 def _assert_grads(case, grads, c, o):
@@ -164,15 +158,12 @@ def test_backward_parity(name, variant, fwd_variant, bwd_variant, sh_drgb):
     C = _C()
     c, o = _covered(name, variant)
     try:
-        C.set_tuning("fwd_variant", fwd_variant)
-        C.set_tuning("bwd_variant", bwd_variant)
         C.set_thread_option("sh_drgb", sh_drgb)
-        fwd = _forward(c)
-        grads = _backward(c, fwd)
-        lean = _backward(c, fwd, lean=True)
+        with G.tuning(fwd_variant=fwd_variant, bwd_variant=bwd_variant):
+            fwd = _forward(c)
+            grads = _backward(c, fwd)
+            lean = _backward(c, fwd, lean=True)
     finally:
-        C.set_tuning("fwd_variant", -1)
-        C.set_tuning("bwd_variant", -1)
         C.set_thread_option("sh_drgb", 1)
     assert G.image_l1(fwd[2][1].cpu().numpy(), o["fwd"].color) < G.IMAGE_L1_TOL
     _assert_grads(f"general_{name}_{variant}_f{fwd_variant}b{bwd_variant}d{sh_drgb}", grads, c, o)
@@ -208,14 +199,12 @@ def _aux_reference(name):
 def test_aux_outputs(name):
     """Depth and alpha maps and their backward: the depth's pull-back onto the
     means is dL_dz V[:3, 2], no longer (0, 0, 1)."""
-    import test_gpu_aux_outputs as TX
-    C = _C()
     c, o = _covered(name)
     ref = _aux_reference(name)
     zaxis = np.asarray(c["cam"].world_view_transform, np.float64)[:3, 2]
     assert np.abs(zaxis).min() > 0.2  # every component of the pull-back matters
-    s, t, sh, col = TX._operands(c["sc"], c["cam"], "sh", c["seed"], bg=BG)
-    K, color, depth, alpha, radii, geom, binning, img = TX._forward(C, C.rasterize_gaussians_aux, s, t, sh, col)
+    fwd = G.native_forward(c["sc"], c["cam"], bg=BG, aux=True, trailing=False)
+    K, color, depth, alpha, radii, geom, binning, img = fwd[2]
     assert K == ref["fwd"].num_rendered
     zmax = float(ref["fwd"].depths[ref["fwd"].radii > 0].max())
     l1a = G.image_l1(alpha.cpu().numpy(), ref["alpha"])
@@ -224,12 +213,12 @@ def test_aux_outputs(name):
     assert G.image_l1(color.cpu().numpy(), ref["fwd"].color) < G.IMAGE_L1_TOL
     assert l1a < G.IMAGE_L1_TOL
     assert l1d < G.IMAGE_L1_TOL * zmax  # the blend is linear in the feature
-    dpix, dd, da = TX._cotangents(c["W"], c["H"], c["seed"])
-    grads = TX._backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, dpix, dd, da)
-    TX._check_against_reference(f"general_aux_{name}", grads, ref, c["sc"], c["cam"], dpix, dd, da)
+    dpix, dd, da = AXR.cotangents(c["W"], c["H"], c["seed"])
+    grads = G.native_backward(fwd, dpix, aux=(dd, da), trailing=False)
+    AXR.check_against_reference(f"general_aux_{name}", grads, ref, c["sc"], c["cam"], dpix, dd, da)
     # the depth cotangent alone
-    grads = TX._backward_aux(C, s, t, sh, col, radii, geom, K, binning, img, None, dd, None)
-    TX._check_against_reference(f"general_aux_depth_{name}", grads, ref, c["sc"], c["cam"], None, dd, None)
+    grads = G.native_backward(fwd, np.zeros((3, c["H"], c["W"]), np.float32), aux=(dd, None), trailing=False)
+    AXR.check_against_reference(f"general_aux_depth_{name}", grads, ref, c["sc"], c["cam"], None, dd, None)
 
 
 # ----------------------------------------------------------------------- 4. AMR
@@ -269,12 +258,9 @@ def test_amr_render_once(interpolate, amr_variant):
     C = _C()
     a = _amr_covered()
     P, W, H = a["P"], a["W"], a["H"]
-    C.set_tuning("amr_variant", amr_variant)
-    try:
+    with G.tuning(amr_variant=amr_variant):
         with torch.no_grad():
             _, _, color, radii, (gb, bb, ib) = _amr_render_once(a, interpolate)
-    finally:
-        C.set_tuning("amr_variant", 4)
     rcol, rrad, st = O.amr_forward(a["s"], foveaStep=-2, interpolate_image=interpolate, **a["kw"])
     np.testing.assert_array_equal(radii.cpu().numpy(), rrad)
     assert not rrad[a["census"]["near_culled_mask"]].any()
@@ -345,7 +331,6 @@ def test_multiview_equals_sum_of_oracle_view_backwards(name):
     """A Gaussian behind one camera and in front of another takes the
     gradient of the views that see it alone (present[])."""
     from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
-    C = _C()
     c, _ = _covered(name)
     cams, want, allow, vis, z = _multiview_reference(name)
     mixed = np.zeros(c["P"], bool)
@@ -355,14 +340,11 @@ def test_multiview_equals_sum_of_oracle_view_backwards(name):
     print(f"{name}: {int(mixed.sum())} Gaussians behind one camera and rendered by another")
     assert int(mixed.sum()) >= 20
     t = G.scene_tensors(c["sc"])
-    e = torch.Tensor([])
     records = []
     for v, cam in enumerate(cams):
         s = G.torch_settings(cam)
         dpix = torch.from_numpy(S.make_cotangent(c["H"], c["W"], 10 + v)).cuda()
-        K, color, radii, geom, binning, img = C.rasterize_gaussians(
-            s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e, s.viewmatrix, s.projmatrix,
-            s.tanfovx, s.tanfovy, s.image_height, s.image_width, t["shs"], 3, s.campos, False, False)
+        K, color, radii, geom, binning, img = G.native_forward(c["sc"], cam, settings=s, tensors=t)[2]
         np.testing.assert_array_equal(radii.cpu().numpy() > 0, vis[v])
         records.append(DP.view_record(s, radii, geom, K, binning, img, dpix))
     got = DP.multiview_param_grads(torch.stack(records), t["means3D"], t["shs"], 3, t["scales"], t["rotations"], 1.0)
@@ -382,10 +364,9 @@ def test_multiview_equals_sum_of_oracle_view_backwards(name):
 # -------------------------------------------------------------- 6. antialiasing
 @functools.lru_cache(maxsize=None)
 def _antialias_reference(name, variant):
-    import test_gpu_antialiasing as TA
     P, W, H, seed, lsm = CASES[name]
     sc, cam, dpix = G.general_case(P, W, H, seed, clamp=False, log_scale_mean=lsm)
-    kw, deg = TA._variant_kw(sc, variant, seed)
+    kw, deg = AR.variant_kw(sc, variant, seed)
     ref = AR.reference_forward(cam, sc.means3D, sc.opacities, kw, sh_degree=deg)
     t64 = lambda a: torch.tensor(np.asarray(a, np.float64))  # noqa: E731
     _, _, inside, _ = AR.coef64(cam, t64(sc.means3D), t64(sc.scales), t64(sc.rotations))
@@ -397,23 +378,23 @@ def _antialias_reference(name, variant):
 def test_antialiasing(name, variant):
     """The antialiased forward and backward under the general camera, on the
     scene that needs no clamp (the reference takes none)."""
-    import test_gpu_antialiasing as TA
     C = _C()
     sc, cam, dpix, kw, deg, ref, inside, rg, al = _antialias_reference(name, variant)
     fwd = ref["fwd"]
     vis = fwd.radii > 0
     assert vis.sum() >= 0.9 * vis.size and inside[vis].all()
     assert not G.clamp_active(sc.means3D, cam)[vis].any()
-    s, t = TA._operands(sc, cam, kw, deg, True)
-    K, color, radii, geom, binning, img = TA._forward(C, s, t)
+    s, t = AR.operands(sc, cam, kw, deg, True)
+    native = G.native_forward(sc, cam, settings=s, tensors=t)
+    K, color, radii, geom, binning, img = native[2]
     assert K == fwd.num_rendered and np.array_equal(radii.cpu().numpy(), fwd.radii)
     P, W, H = sc.means3D.shape[0], cam.image_width, cam.image_height
     d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
     co = d["conic_opacity"].cpu().numpy()
-    assert np.array_equal(TA._bits(co[vis, 3]), TA._bits(ref["o_eff"][vis, 0]))
-    assert np.array_equal(TA._bits(co[vis, :3]), TA._bits(fwd.conic_opacity[vis, :3]))
+    assert np.array_equal(AR.bits(co[vis, 3]), AR.bits(ref["o_eff"][vis, 0]))
+    assert np.array_equal(AR.bits(co[vis, :3]), AR.bits(fwd.conic_opacity[vis, :3]))
     l1 = G.image_l1(color.cpu().numpy(), fwd.color)
     print(f"antialias general {name} {variant}: image L1 {l1:.3e}")
     assert l1 < G.IMAGE_L1_TOL
-    grads = TA._backward(C, s, t, radii, geom, K, binning, img, dpix)
-    TA._check_grads(f"general_antialias_{name}_{variant}", grads, rg, al, sc, cam, fwd)
+    grads = G.native_backward(native, dpix)
+    AR.check_grads(f"general_antialias_{name}_{variant}", grads, rg, al, sc, cam, fwd)

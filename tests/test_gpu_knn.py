@@ -93,8 +93,8 @@ def test_transposed_view_gives_the_contiguous_bits():
 # ------------------------------------------------------------- the C ABI ----
 def _knn_capi(pts):
     """gs_simple_knn through ctypes into an output pre-filled with NaN."""
-    import test_gpu_capi_ctypes as CT
-    lib = CT._lib()
+    import capi_helpers as CT
+    lib = CT.lib()
     lib.gs_simple_knn.argtypes = [CT.I, CT.VP, CT.VP, CT.GsBuffer, CT.VP]
     lib.gs_simple_knn.restype = CT.I
     P = len(pts)
@@ -102,7 +102,7 @@ def _knn_capi(pts):
     out = torch.full((P,), float("nan"), dtype=torch.float32, device="cuda")
     bufs = CT.Buffers(dev.device)
     stream = torch.cuda.current_stream()
-    CT._check(lib, lib.gs_simple_knn(P, CT._p(dev), CT._p(out), bufs.buf("scratch"), ctypes.c_void_p(stream.cuda_stream)),
+    CT.check(lib, lib.gs_simple_knn(P, CT.ptr(dev), CT.ptr(out), bufs.buf("scratch"), ctypes.c_void_p(stream.cuda_stream)),
               "gs_simple_knn")
     stream.synchronize()
     return out.cpu().numpy()

@@ -28,18 +28,11 @@ def _views(P, W, H, yaws, seed=0):
 
 
 def _forward(C, s, t, deg=3):
-    e = torch.Tensor([])
-    return C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e,
-                                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-                                 t["shs"], deg, s.campos, False, False)
+    return G.native_forward(None, None, settings=s._replace(sh_degree=deg), tensors=t)[2]
 
 
 def _full_backward(C, s, t, fwd, dpix, deg=3):
-    K, color, radii, geom, binning, img = fwd
-    e = torch.Tensor([])
-    return C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                          s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], deg,
-                                          s.campos, geom, K, binning, img, False)
+    return G.native_backward((s._replace(sh_degree=deg), t, fwd), dpix)
 
 
 @pytest.mark.parametrize("yaws,deg", [((0.0,), 3), ((-5.0, 0.0, 5.0), 3), ((-12.0, -3.0, 4.0, 9.0, 15.0), 3),

@@ -13,40 +13,7 @@ import gs_helpers as G
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-CASES = [
-    ("g1_64_32x32", 64, 32, 32, 3),
-    ("cfg1_10k_256", 10000, 256, 256, 0),
-    ("ragged_3k_250x130", 3000, 250, 130, 7),
-    ("dense_20k_128", 20000, 128, 128, 11),  # large tiles: exercises the merge-sort path
-    ("grid_17k_tiles", 3000, 2112, 2080, 5),  # T = 17160 > kLdsTiles: device-atomic binning path
-]
-
-
-def _gpu_forward(sc, cam, colors_precomp=None, cov3D_precomp=None, bg=(0.0, 0.0, 0.0), keep_scales=False):
-    import gaussian_splatting_with_eye_tracking_amd._C as C
-    s = G.torch_settings(cam, bg=bg)
-    t = G.scene_tensors(sc)
-    e = torch.Tensor([])
-    sh = t["shs"] if colors_precomp is None else e
-    col = e if colors_precomp is None else torch.from_numpy(colors_precomp).cuda()
-    scales = t["scales"] if cov3D_precomp is None or keep_scales else e
-    rots = t["rotations"] if cov3D_precomp is None or keep_scales else e
-    cov = e if cov3D_precomp is None else torch.from_numpy(cov3D_precomp).cuda()
-    out = C.rasterize_gaussians(s.bg, t["means3D"], col, t["opacities"], scales, rots, s.scale_modifier, cov,
-                                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh,
-                                s.sh_degree, s.campos, s.prefiltered, s.debug)
-    torch.cuda.synchronize()
-    return s, t, out
-
-
-def _oracle_forward(sc, cam, colors_precomp=None, cov3D_precomp=None, bg=(0.0, 0.0, 0.0), keep_scales=False):
-    import oracle as O
-    s = O.settings_from_camera(cam, bg=bg)
-    both = cov3D_precomp is None or keep_scales
-    kw = dict(shs=sc.shs if colors_precomp is None else None, colors_precomp=colors_precomp,
-              scales=sc.scales if both else None,
-              rotations=sc.rotations if both else None, cov3D_precomp=cov3D_precomp)
-    return s, O.forward(s, sc.means3D, sc.opacities, **kw), kw
+CASES = G.PARITY_CASES
 
 
 @pytest.mark.parametrize("name,P,W,H,seed", CASES)
@@ -59,10 +26,10 @@ def _forward_buffers_bit_exact(name, P, W, H, seed):
     sc, cam = G.scene_and_camera(P, W, H, seed)
     C.set_thread_option("store_cov3d", 1)  # the geometry buffer's cov3D is written on request only
     try:
-        _, _, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam)
+        _, _, (K, color, radii, geom, binning, img) = G.native_forward(sc, cam)
     finally:
         C.set_thread_option("store_cov3d", 0)
-    _, ref, _ = _oracle_forward(sc, cam)
+    _, ref, _ = G.oracle_forward(sc, cam)
     assert K == ref.num_rendered
     d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
     np.testing.assert_array_equal(radii.cpu().numpy(), ref.radii)
@@ -86,8 +53,8 @@ def _forward_buffers_bit_exact(name, P, W, H, seed):
 def test_forward_image(name, P, W, H, seed):
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(P, W, H, seed)
-    _, _, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam, bg=(0.1, 0.2, 0.3))
-    _, ref, _ = _oracle_forward(sc, cam, bg=(0.1, 0.2, 0.3))
+    _, _, (K, color, radii, geom, binning, img) = G.native_forward(sc, cam, bg=(0.1, 0.2, 0.3))
+    _, ref, _ = G.oracle_forward(sc, cam, bg=(0.1, 0.2, 0.3))
     assert G.image_l1(color.cpu().numpy(), ref.color) < G.IMAGE_L1_TOL
     d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
     ncont = d["n_contrib"].cpu().numpy().astype(np.uint32)
@@ -113,27 +80,17 @@ def test_backward_parity(name, P, W, H, seed, variant):
         colors = np.random.default_rng(seed + 5).uniform(0, 1, (P, 3)).astype(np.float32)
     both = variant == "cov3D_precomp_and_scales"
     if variant.startswith("cov3D_precomp"):
-        _, r0, _ = _oracle_forward(sc, cam)
+        _, r0, _ = G.oracle_forward(sc, cam)
         cov = r0.cov3D.copy()
         # invisible Gaussians have no computed cov3D: give them a valid one
         cov[r0.radii <= 0] = np.array([1e-4, 0, 0, 1e-4, 0, 1e-4], np.float32)
         if both:
             cov *= np.float32(1.3)
     bg = (0.2, 0.1, 0.05)
-    s, t, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam, colors, cov, bg=bg, keep_scales=both)
-    os_, ref, kw = _oracle_forward(sc, cam, colors, cov, bg=bg, keep_scales=both)
+    fwd = G.native_forward(sc, cam, colors, cov, bg=bg, keep_scales=both)
+    os_, ref, kw = G.oracle_forward(sc, cam, colors, cov, bg=bg, keep_scales=both)
     dpix = S.make_cotangent(H, W, seed + 1)
-    import gaussian_splatting_with_eye_tracking_amd._C as C
-    e = torch.Tensor([])
-    sh = t["shs"] if colors is None else e
-    colt = e if colors is None else torch.from_numpy(colors).cuda()
-    scales = t["scales"] if cov is None or both else e
-    rots = t["rotations"] if cov is None or both else e
-    covt = e if cov is None else torch.from_numpy(cov).cuda()
-    grads = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, colt, scales, rots, s.scale_modifier, covt,
-                                           s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                           torch.from_numpy(dpix).cuda(), sh, s.sh_degree, s.campos, geom, K, binning,
-                                           img, False)
+    grads = G.native_backward(fwd, dpix)
     names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
              "dL_drotations"]
     rg = O.backward(os_, ref, sc.means3D, dpix, **kw)
@@ -146,10 +103,7 @@ def test_backward_parity(name, P, W, H, seed, variant):
     G.assert_grads_elementwise(f"backward_{name}_{variant}", names, grads, rg, sc, cam, ref, allow=al, ties=ties)
     # the autograd wrappers' binding: the same bits, colour / covariance
     # gradients only when their precomputed input was given
-    lean = C.rasterize_gaussians_backward_lean(s.bg, t["means3D"], radii, colt, scales, rots, s.scale_modifier, covt,
-                                               s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                               torch.from_numpy(dpix).cuda(), sh, s.sh_degree, s.campos, geom, K,
-                                               binning, img, False)
+    lean = G.native_backward(fwd, dpix, lean=True)
     for n, g, gl in zip(names, grads, lean):
         if (n == "dL_dcolors" and colors is None) or (n == "dL_dcov3D" and cov is None):
             assert gl.numel() == 0, n
@@ -198,9 +152,9 @@ def test_binning_forms_bit_exact(P, W, H):
     the duplicate speculatively)."""
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(P, W, H, 12)
-    _gpu_forward(sc, cam)
-    _, _, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam)
-    _, ref, _ = _oracle_forward(sc, cam)
+    G.native_forward(sc, cam)
+    _, _, (K, color, radii, geom, binning, img) = G.native_forward(sc, cam)
+    _, ref, _ = G.oracle_forward(sc, cam)
     assert K == ref.num_rendered
     d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
     np.testing.assert_array_equal(d["ranges"].cpu().numpy().astype(np.uint32), ref.ranges)
@@ -248,12 +202,9 @@ def test_tile_sort_adversarial_depths(kind, sort_algo):
     P, W, H = 100000, 256, 192
     cam = S.make_camera(W, H)
     sc = _clustered_scene(P, cam, 5, kind)
-    C.set_tuning("sort_algo", sort_algo)
-    try:
-        _, _, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam)
-    finally:
-        C.set_tuning("sort_algo", 1)
-    _, ref, _ = _oracle_forward(sc, cam)
+    with G.tuning(sort_algo=sort_algo):
+        _, _, (K, color, radii, geom, binning, img) = G.native_forward(sc, cam)
+    _, ref, _ = G.oracle_forward(sc, cam)
     assert K == ref.num_rendered
     n = ref.ranges[:, 1] - ref.ranges[:, 0]
     assert all(((n > a) & (n <= b)).any() for a, b in ((1, 1024), (1024, 2048), (2048, 4096), (4096, 1 << 30)))
@@ -272,7 +223,6 @@ def test_backward_with_unfilled_work_buckets():
     import ctypes
     import os
     import gaussian_splatting_with_eye_tracking_amd as pkg
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     P, W, H, seed = 3000, 250, 130, 7
     sc, cam = G.scene_and_camera(P, W, H, seed)
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
@@ -282,15 +232,12 @@ def test_backward_with_unfilled_work_buckets():
     base = 1 << 20
     assert lib.gs_image_view_of(ctypes.c_void_p(base), W, H, 16, ctypes.byref(view)) == 0
     off = view[15] - base  # bucket_count
-    e = torch.Tensor([])
     out = []
     for corrupt in (False, True):
-        s, t, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam)
+        fwd = G.native_forward(sc, cam)
         if corrupt:
-            img[off:off + 1024].zero_()
-        g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"],
-                                           s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                           dpix, t["shs"], s.sh_degree, s.campos, geom, K, binning, img, False)
+            fwd[2][5][off:off + 1024].zero_()
+        g = G.native_backward(fwd, dpix)
         out.append([x.cpu().numpy() for x in g])
     for a, b in zip(*out):
         assert np.all(np.isfinite(b))
@@ -316,8 +263,9 @@ def test_config2_full_size_parity_and_psnr():
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     P, W, H = 1_000_000, 1920, 1080
     sc, cam = G.scene_and_camera(P, W, H, 0)
-    s, t, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam)
-    os_, ref, kw = _oracle_forward(sc, cam)
+    fwd = G.native_forward(sc, cam)
+    K, color, radii, geom, binning, img = fwd[2]
+    os_, ref, kw = G.oracle_forward(sc, cam)
     assert K == ref.num_rendered
     d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
     np.testing.assert_array_equal(radii.cpu().numpy(), ref.radii)
@@ -330,11 +278,7 @@ def test_config2_full_size_parity_and_psnr():
     assert abs(_psnr(got, gt) - _psnr(ref.color, gt)) < 0.01
     assert _psnr(got, ref.color) > 80.0
     dpix = S.make_cotangent(H, W, 1)
-    e = torch.Tensor([])
-    grads = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"],
-                                           s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                           torch.from_numpy(dpix).cuda(), t["shs"], s.sh_degree, s.campos, geom, K,
-                                           binning, img, False)
+    grads = G.native_backward(fwd, dpix)
     rg = O.backward(os_, ref, sc.means3D, dpix, **kw)
     names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
              "dL_drotations"]
@@ -351,25 +295,15 @@ def test_blend_geometries_match_oracle(fwd_variant, bwd_variant):
     every pairing, against the oracle (the fallback forward leaves no hit
     codes: the backward then culls by geometry)."""
     import oracle as O
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     P, W, H, seed = 10000, 256, 256, 0
     sc, cam = G.scene_and_camera(P, W, H, seed)
-    try:
-        C.set_tuning("fwd_variant", fwd_variant)
-        C.set_tuning("bwd_variant", bwd_variant)
-        s, t, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam, bg=(0.2, 0.1, 0.05))
-        dpix = S.make_cotangent(H, W, seed + 1)
-        e = torch.Tensor([])
-        grads = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"],
-                                               s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx,
-                                               s.tanfovy, torch.from_numpy(dpix).cuda(), t["shs"], s.sh_degree,
-                                               s.campos, geom, K, binning, img, False)
-        torch.cuda.synchronize()
-    finally:
-        C.set_tuning("fwd_variant", -1)
-        C.set_tuning("bwd_variant", -1)
-    os_, ref, kw = _oracle_forward(sc, cam, bg=(0.2, 0.1, 0.05))
+    dpix = S.make_cotangent(H, W, seed + 1)
+    with G.tuning(fwd_variant=fwd_variant, bwd_variant=bwd_variant):
+        fwd = G.native_forward(sc, cam, bg=(0.2, 0.1, 0.05))
+        grads = G.native_backward(fwd, dpix)
+    color = fwd[2][1]
+    os_, ref, kw = G.oracle_forward(sc, cam, bg=(0.2, 0.1, 0.05))
     assert G.image_l1(color.cpu().numpy(), ref.color) < G.IMAGE_L1_TOL
     rg = O.backward(os_, ref, sc.means3D, dpix, **kw)
     names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
@@ -432,7 +366,6 @@ def test_speculative_duplicate_matches_synchronous():
     10k one), a call within it must keep it; images and gradients are
     bit-identical to the synchronous path (tuning "spec_dup" 0)."""
     from diff_gaussian_rasterization import GaussianRasterizer
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     scenes = [G.scene_and_camera(P, 256, 192, seed) for P, seed in ((10000, 0), (30000, 1), (30000, 1), (8000, 2))]
 
     def run():
@@ -447,13 +380,10 @@ def test_speculative_duplicate_matches_synchronous():
             out.append((color.detach().clone(), radii.clone()) + tuple(x.clone() for x in g))
         return out
 
-    try:
-        C.set_tuning("spec_dup", 0)
+    with G.tuning(spec_dup=0):
         ref = run()
-        C.set_tuning("spec_dup", 1)
+    with G.tuning(spec_dup=1):
         spec = run()
-    finally:
-        C.set_tuning("spec_dup", 1)
     for i, (a, b) in enumerate(zip(ref, spec)):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), i
         for x, y in zip(a[2:], b[2:]):
@@ -476,31 +406,26 @@ def test_all_culled():
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(500, 64, 48)
     sc.means3D[:, 2] = -5.0
-    s, t, (K, color, radii, geom, binning, img) = _gpu_forward(sc, cam, bg=(0.5, 0.25, 0.125))
+    s, t, (K, color, radii, geom, binning, img) = G.native_forward(sc, cam, bg=(0.5, 0.25, 0.125))
     assert K == 0 and torch.all(radii == 0)
     np.testing.assert_allclose(color.cpu().numpy()[:, 0, 0], [0.5, 0.25, 0.125])
 
 
 def test_prefiltered_violation_raises():
     from diff_gaussian_rasterization import GaussianRasterizationSettings
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(100, 32, 32)
     sc.means3D[0, 2] = -1.0
-    s = G.torch_settings(cam)
+    s = G.torch_settings(cam)._replace(prefiltered=True)
     t = G.scene_tensors(sc)
     with pytest.raises(RuntimeError, match="prefiltered"):
-        C.rasterize_gaussians(s.bg, t["means3D"], torch.Tensor([]), t["opacities"], t["scales"], t["rotations"], 1.0,
-                              torch.Tensor([]), s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, 32, 32, t["shs"], 3,
-                              s.campos, True, False)
+        G.native_forward(sc, cam, settings=s, tensors=t)
     # the header is not zeroed per call: the next calls (the caching allocator
     # hands back the same geometry bytes, stale error word included) must not
     # raise once every point is in front of the camera
     ok = t["means3D"].clone()
     ok[0, 2] = 5.0
     for _ in range(3):
-        out = C.rasterize_gaussians(s.bg, ok, torch.Tensor([]), t["opacities"], t["scales"], t["rotations"], 1.0,
-                                    torch.Tensor([]), s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, 32, 32,
-                                    t["shs"], 3, s.campos, True, False)
+        out = G.native_forward(sc, cam, settings=s, tensors=dict(t, means3D=ok))[2]
         assert out[0] > 0
 
 
@@ -542,11 +467,8 @@ def test_amr_foveated_steps(name, P, W, H, seed, amr_variant):
     import oracle as O
     import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(P, W, H, seed)
-    C.set_tuning("amr_variant", amr_variant)
-    try:
+    with G.tuning(amr_variant=amr_variant):
         acc, radii, steps, (gb, bb, ib) = _amr_gpu_steps(sc, cam, bg=(0.1, 0.1, 0.1))
-    finally:
-        C.set_tuning("amr_variant", 4)
     s = O.settings_from_camera(cam, bg=(0.1, 0.1, 0.1))
     kw = dict(means3D=sc.means3D, opacities=sc.opacities, shs=sc.shs, scales=sc.scales, rotations=sc.rotations)
     racc, rradii, st, rsteps = O.amr_render_foveated(s, kw)
@@ -615,11 +537,8 @@ def test_amr_variants_bit_identical(P, W, H, seed):
     sc, cam = G.scene_and_camera(P, W, H, seed)
     out = {}
     for v in (4, 0):
-        C.set_tuning("amr_variant", v)
-        try:
+        with G.tuning(amr_variant=v):
             acc, radii, steps, (gb, bb, ib) = _amr_gpu_steps(sc, cam, bg=(0.1, 0.2, 0.3))
-        finally:
-            C.set_tuning("amr_variant", 4)
         d = C.parse_buffers(gb, bb, ib, P, 0, W, H, 32)
         K = int(d["hdr"][0].item())
         d = C.parse_buffers(gb, bb, ib, P, K, W, H, 32)
@@ -655,18 +574,14 @@ def test_amr_steps_with_nothing_in_front():
 @pytest.mark.parametrize("amr_variant", [4, 0])
 def test_amr_render_once_interpolated(amr_variant):
     import oracle as O
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from diff_gaussian_rasterization_amr import GaussianRasterizer
     sc, cam = G.scene_and_camera(8000, 224, 160, 5)
     s = G.torch_settings(cam, amr=True)
     t = G.scene_tensors(sc)
-    C.set_tuning("amr_variant", amr_variant)
-    try:
+    with G.tuning(amr_variant=amr_variant):
         color, radii, gb, bb, ib = GaussianRasterizer(s)(
             means3D=t["means3D"], means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], shs=t["shs"],
             scales=t["scales"], rotations=t["rotations"], foveaStep=-2, interpolate_image=True)
-    finally:
-        C.set_tuning("amr_variant", 4)
     os_ = O.settings_from_camera(cam)
     rcol, rrad, st = O.amr_render_once(os_, dict(means3D=sc.means3D, opacities=sc.opacities, shs=sc.shs,
                                                   scales=sc.scales, rotations=sc.rotations))
@@ -834,35 +749,24 @@ def test_fovea_levels_after_forward_invalidates_saved_buffer():
 def test_bindings_reject_misplaced_operands():
     """A host tensor, a short array or a wrong dtype raises a Python error in
     the binding instead of reaching a kernel as a raw pointer."""
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     sc, cam = G.scene_and_camera(300, 64, 48, 3)
     s = G.torch_settings(cam)
     t = G.scene_tensors(sc)
-    e = torch.Tensor([])
 
     def fwd(**over):
-        a = dict(bg=s.bg, means3D=t["means3D"], colors=e, opacity=t["opacities"], scales=t["scales"],
-                 rotations=t["rotations"], cov=e, sh=t["shs"])
-        a.update(over)
-        return C.rasterize_gaussians(a["bg"], a["means3D"], a["colors"], a["opacity"], a["scales"], a["rotations"],
-                                     1.0, a["cov"], s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, 48, 64,
-                                     a["sh"], 3, s.campos, False, False)
+        return G.native_forward(sc, cam, settings=s, tensors=dict(t, **over))
     with pytest.raises(RuntimeError, match="opacities"):
-        fwd(opacity=t["opacities"].cpu())
+        fwd(opacities=t["opacities"].cpu())
     with pytest.raises(RuntimeError, match="scales"):
         fwd(scales=t["scales"][:100])
     with pytest.raises(RuntimeError, match="rotations"):
         fwd(rotations=t["rotations"].double())
-    K, color, radii, geom, binning, img = fwd()
+    _, tf, (K, color, radii, geom, binning, img) = fwd()
     dpix = torch.zeros_like(color)
     with pytest.raises(RuntimeError, match="radii"):
-        C.rasterize_gaussians_backward(s.bg, t["means3D"], radii.cpu(), e, t["scales"], t["rotations"], 1.0, e,
-                                       s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], 3, s.campos,
-                                       geom, K, binning, img, False)
+        G.native_backward((s, tf, (K, color, radii.cpu(), geom, binning, img)), dpix)
     with pytest.raises(RuntimeError, match="sh"):
-        C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                       s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"][:10], 3,
-                                       s.campos, geom, K, binning, img, False)
+        G.native_backward((s, dict(tf, shs=t["shs"][:10]), (K, color, radii, geom, binning, img)), dpix)
 
 
 # ---------------------------------------------------------- simple-knn ----
@@ -928,13 +832,7 @@ def test_forward_only_hint_from_autograd_wrapper():
         assert step0(False) == 0
     assert step0(True) == 1
     assert step0(False) == 0  # grad mode on, nothing requires a gradient
-    s = G.torch_settings(cam)
-    tg = G.scene_tensors(sc)
-    out = C.rasterize_gaussians(s.bg, tg["means3D"], e, tg["opacities"], tg["scales"], tg["rotations"],
-                                s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                s.image_height, s.image_width, tg["shs"], s.sh_degree, s.campos, s.prefiltered,
-                                s.debug)
-    torch.cuda.synchronize()
+    out = G.native_forward(sc, cam)[2]
     geom = out[3]
     assert int(C.parse_buffers(geom, out[4], out[5], P, 0, W, H, 16)["hdr"][7].item()) == 1
 
@@ -956,12 +854,7 @@ def test_forward_only_hint_cleared_when_the_forward_raises():
         bad = t["means3D"][:, :2].contiguous()  # not [P, 3]: the native forward refuses it
         r(means3D=bad, means2D=torch.zeros_like(t["means3D"]), opacities=t["opacities"], shs=t["shs"],
           scales=t["scales"], rotations=t["rotations"])
-    e = torch.empty(0, device="cuda")
-    out = C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"],
-                                s.scale_modifier, e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                s.image_height, s.image_width, t["shs"], s.sh_degree, s.campos, s.prefiltered,
-                                s.debug)
-    torch.cuda.synchronize()
+    out = G.native_forward(sc, cam, settings=s, tensors=t)[2]
     assert int(C.parse_buffers(out[3], out[4], out[5], P, 0, W, H, 16)["hdr"][7].item()) == 1
 
 
@@ -979,38 +872,22 @@ def test_hit_codes_and_point_list_repeatable():
     cam = S.make_orbit_camera(W, H, 4.0)
     s = G.torch_settings(cam)
     t = G.scene_tensors(sc)
-    e = torch.Tensor([])
 
-    def fwd():
-        return C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e,
-                                     s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, H, W, t["shs"], 3, s.campos,
-                                     False, False)
-
-    C.set_tuning("sort_algo", 0)
-    try:
-        K0, c0, r0, g0, b0, i0 = fwd()
+    with G.tuning(sort_algo=0):
+        K0, c0, r0, g0, b0, i0 = G.native_forward(sc, cam, settings=s, tensors=t)[2]
         want = C.parse_buffers(g0, b0, i0, P, K0, W, H, 16)["point_list"].cpu()
-    finally:
-        C.set_tuning("sort_algo", 1)
     dpix = torch.from_numpy(S.make_cotangent(H, W, 7)).cuda()
     for _ in range(20):
-        K, color, radii, geom, binning, img = fwd()
+        f = G.native_forward(sc, cam, settings=s, tensors=t)
+        K, color, radii, geom, binning, img = f[2]
         assert K == K0
         d = C.parse_buffers(geom, binning, img, P, K, W, H, 16)
         assert torch.equal(d["point_list"].cpu(), want)
         assert torch.equal(color.cpu(), c0.cpu())
         assert int(d["hdr"][6].item()) != 0 and "hit_codes" in d
-    g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                       s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], 3,
-                                       s.campos, geom, K, binning, img, False)
-    C.set_tuning("bwd_variant", 0)
-    try:
-        gf = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], 1.0, e,
-                                            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, dpix, t["shs"], 3,
-                                            s.campos, geom, K, binning, img, False)
-    finally:
-        C.set_tuning("bwd_variant", -1)
-    torch.cuda.synchronize()
+    g = G.native_backward(f, dpix)
+    with G.tuning(bwd_variant=0):
+        gf = G.native_backward(f, dpix)
     for a, b in zip(g[:3], gf[:3]):  # dL_dmeans2D, dL_dcolors, dL_dopacity
         assert G.rel_err(a.cpu().numpy(), b.cpu().numpy()) < 1e-5
 
@@ -1026,11 +903,8 @@ def test_amr_fused_tile_sort_matches_separate_sort(P, W, H, seed):
     sc, cam = G.scene_and_camera(P, W, H, seed)
     out = {}
     for algo in (0, 1, 1):
-        C.set_tuning("sort_algo", algo)
-        try:
+        with G.tuning(sort_algo=algo):
             acc, radii, steps, (gb, bb, ib) = _amr_gpu_steps(sc, cam, bg=(0.1, 0.2, 0.3))
-        finally:
-            C.set_tuning("sort_algo", 1)
         K = int(C.parse_buffers(gb, bb, ib, P, 0, W, H, 32)["hdr"][0].item())
         d = C.parse_buffers(gb, bb, ib, P, K, W, H, 32)
         r = [d["point_list"].cpu(), d["region_count"].cpu()] + [s_.cpu() for s_ in steps]

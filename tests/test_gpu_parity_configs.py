@@ -41,29 +41,14 @@ def oracle_threads():
 
 
 def _c_forward(sc, cam, bg=(0.0, 0.0, 0.0), sh_degree=3, scale_modifier=1.0, shs=None):
-    import gaussian_splatting_with_eye_tracking_amd._C as C
-    s = G.torch_settings(cam, bg=bg, sh_degree=sh_degree, scale_modifier=scale_modifier)
     t = G.scene_tensors(sc)
     if shs is not None:
         t["shs"] = torch.from_numpy(np.ascontiguousarray(shs)).cuda()
-    e = torch.Tensor([])
-    out = C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], s.scale_modifier,
-                                e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-                                t["shs"], s.sh_degree, s.campos, s.prefiltered, s.debug)
-    torch.cuda.synchronize()
-    return s, t, out
+    return G.native_forward(sc, cam, bg=bg, tensors=t, sh_degree=sh_degree, scale_modifier=scale_modifier)
 
 
 def _c_backward(s, t, out, dpix):
-    import gaussian_splatting_with_eye_tracking_amd._C as C
-    K, color, radii, geom, binning, img = out
-    e = torch.Tensor([])
-    g = C.rasterize_gaussians_backward(s.bg, t["means3D"], radii, e, t["scales"], t["rotations"], s.scale_modifier, e,
-                                       s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy,
-                                       torch.from_numpy(dpix).cuda(), t["shs"], s.sh_degree, s.campos, geom, K,
-                                       binning, img, False)
-    torch.cuda.synchronize()
-    return g
+    return G.native_backward((s, t, out), dpix)
 
 
 def _check_binning(C, out, ref, P, W, H, tile=16):
@@ -290,13 +275,11 @@ def test_config5_eight_views_one_gpu(oracle_threads):
     backwards (1e-5 relative: float-atomic order noise), and view 0 alone
     matches the oracle."""
     O = oracle_threads
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from gaussian_splatting_with_eye_tracking_amd import data_parallel as DP
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     P, W, H = 1_000_000, 1920, 1080
     sc, _ = G.scene_and_camera(P, W, H, 0)
     t = G.scene_tensors(sc)
-    e = torch.Tensor([])
     yaws = S.config5_yaws(8)
     recs = []
     summed = None
@@ -307,13 +290,11 @@ def test_config5_eight_views_one_gpu(oracle_threads):
     for v, yaw in enumerate(yaws):
         cam = S.make_orbit_camera(W, H, yaw)
         s = G.torch_settings(cam)
-        out = C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], 1.0, e,
-                                    s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, H, W, t["shs"], 3, s.campos,
-                                    False, False)
+        _, tf, out = G.native_forward(sc, cam, settings=s, tensors=t)
         K, color, radii, geom, binning, img = out
         dpix = S.make_cotangent(H, W, 100 + v)
         recs.append(DP.view_record(s, radii, geom, K, binning, img, torch.from_numpy(dpix).cuda()))
-        g = _c_backward(s, t, out, dpix)
+        g = _c_backward(s, tf, out, dpix)
         per = [g[3], g[5], g[2], g[6], g[7]]  # means3D, sh, opacity, scales, rotations
         summed = [x.double().clone() for x in per] if summed is None else [a + b.double() for a, b in zip(summed, per)]
         del out

@@ -19,41 +19,26 @@ pytestmark = pytest.mark.gpu
 
 
 def _forward(sc, cam):
-    import gaussian_splatting_with_eye_tracking_amd._C as C
-    s = G.torch_settings(cam)
-    t = G.scene_tensors(sc)
-    e = torch.Tensor([])
-    out = C.rasterize_gaussians(s.bg, t["means3D"], e, t["opacities"], t["scales"], t["rotations"], s.scale_modifier,
-                                e, s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width,
-                                t["shs"], s.sh_degree, s.campos, s.prefiltered, s.debug)
-    torch.cuda.synchronize()
-    K, color, radii = out[0], out[1], out[2]
+    K, color, radii = G.native_forward(sc, cam)[2][:3]
     return int(K), color.cpu().numpy(), radii.cpu().numpy()
 
 
 @pytest.mark.parametrize("mode", [2])
 def test_readback_modes_match_copy(mode):
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     scenes = [G.scene_and_camera(P, W, H, seed) for P, W, H, seed in
               ((10000, 256, 256, 0), (30000, 320, 200, 3), (5000, 256, 256, 1))]
-    ref = []
-    try:
-        C.set_tuning("hdr_mirror", 0)
-        for sc, cam in scenes:
-            ref.append(_forward(sc, cam))
-        C.set_tuning("hdr_mirror", mode)
+    with G.tuning(hdr_mirror=0):
+        ref = [_forward(sc, cam) for sc, cam in scenes]
+    with G.tuning(hdr_mirror=mode):
         for rep in range(3):
             for (sc, cam), (K0, c0, r0) in zip(scenes, ref):
                 K, c, r = _forward(sc, cam)
                 assert K == K0, (mode, rep, K, K0)
                 assert np.array_equal(c, c0), (mode, rep)
                 assert np.array_equal(r, r0), (mode, rep)
-    finally:
-        C.set_tuning("hdr_mirror", 2)
 
 
 def test_readback_poll_amr_step0():
-    import gaussian_splatting_with_eye_tracking_amd._C as C
     from diff_gaussian_rasterization_amr import _RasterizeGaussians
     from gaussian_splatting_with_eye_tracking_amd import synthetic as S
     import bench
@@ -77,11 +62,8 @@ def test_readback_poll_amr_step0():
         torch.cuda.synchronize()
         return acc.cpu().numpy()
 
-    try:
-        C.set_tuning("hdr_mirror", 0)
+    with G.tuning(hdr_mirror=0):
         ref = frame()
-        C.set_tuning("hdr_mirror", 2)
+    with G.tuning(hdr_mirror=2):
         for _ in range(2):
             assert np.array_equal(frame(), ref)
-    finally:
-        C.set_tuning("hdr_mirror", 2)

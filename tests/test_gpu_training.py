@@ -38,14 +38,6 @@ def _T():
     return training
 
 
-def raw_from_scene(sc, device="cuda"):
-    from gaussian_splatting_with_eye_tracking_amd import ply
-    g = ply.from_activated(sc.means3D, sc.opacities, sc.scales, sc.rotations, sc.shs)
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)  # noqa: E731
-    return {"xyz": t(g.xyz), "f_dc": t(g.features_dc), "f_rest": t(g.features_rest), "opacity": t(g.opacity),
-            "scaling": t(g.scaling), "rotation": t(g.rotation)}
-
-
 def oracle_from(m):
     """An OracleModel in exactly m's state (params, grads, moments, steps, statistics, lrs)."""
     T = _T()
@@ -129,7 +121,7 @@ def _render_case(P=3000, W=128, H=96, seed=0):
 def test_densify_stats_kernel_matches_reference():
     T = _T()
     sc, cam, s = _render_case()
-    m = T.FlatGaussianModel(raw_from_scene(sc), 3, 1.0)
+    m = T.FlatGaussianModel(G.raw_from_scene(sc), 3, 1.0)
     m.active_sh_degree = 3
     pkg = m.render(s)
     (pkg["render"] * torch.randn_like(pkg["render"])).sum().backward()
@@ -152,7 +144,7 @@ def test_post_backward_lockstep_with_reference(iteration, fused):
     densification (4000, opacity step count lagging)."""
     T = _T()
     sc, cam, s = _render_case(seed=iteration)
-    m = T.FlatGaussianModel(raw_from_scene(sc), 3, spatial_lr_scale=5.0)
+    m = T.FlatGaussianModel(G.raw_from_scene(sc), 3, spatial_lr_scale=5.0)
     m.active_sh_degree = 3
     gen = torch.Generator().manual_seed(iteration)
     # a state mid-training: moments, step counts (opacity one behind), statistics
@@ -205,7 +197,7 @@ def _truncate_sh(raw, max_sh_degree):
 def _fused_vs_autograd(P, max_sh_degree, active_sh):
     T = _T()
     sc, cam, s = _render_case(P=P, W=160, H=120, seed=9)
-    raw = _truncate_sh(raw_from_scene(sc), max_sh_degree)
+    raw = _truncate_sh(G.raw_from_scene(sc), max_sh_degree)
     raw["rotation"] = raw["rotation"] * torch.linspace(0.5, 2.0, P, device="cuda")[:, None]  # unnormalised
     gt = torch.rand(3, 120, 160, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
     out = []
@@ -254,7 +246,7 @@ def test_fused_accumulate_sums_two_views():
     sc, cam, s_a = _render_case(P=P, W=160, H=120, seed=11)
     cam_b = G.S.make_camera(160, 120, R=G._rot("y", 14.0) @ G._rot("x", -6.0), T=np.array([0.35, -0.1, 0.4]))
     s_b = G.torch_settings(cam_b)
-    raw = raw_from_scene(sc)
+    raw = G.raw_from_scene(sc)
     gen = torch.Generator("cuda").manual_seed(3)
     gts = [torch.rand(3, 120, 160, device="cuda", generator=gen) for _ in range(2)]
 
@@ -306,7 +298,7 @@ def _densified_model(seed, fused=True):
     T = _T()
     iteration = 3000
     sc, cam, s = _render_case(P=3000, W=160, H=120, seed=seed)
-    m = T.FlatGaussianModel(raw_from_scene(sc), 3, spatial_lr_scale=5.0)
+    m = T.FlatGaussianModel(G.raw_from_scene(sc), 3, spatial_lr_scale=5.0)
     m.active_sh_degree = 3
     gen = torch.Generator().manual_seed(seed)
     for g in T.GROUPS:
@@ -358,7 +350,7 @@ def test_training_run_fits_a_target():
     sc2, _ = G.scene_and_camera(4000, 160, 120, seed=4)
     opt = T.OptimizationParams(densify_from_iter=20, densification_interval=20, opacity_reset_interval=1000,
                                densify_until_iter=80, iterations=10_000)
-    m = T.FlatGaussianModel(raw_from_scene(sc2), 3, spatial_lr_scale=5.0, opt=opt)
+    m = T.FlatGaussianModel(G.raw_from_scene(sc2), 3, spatial_lr_scale=5.0, opt=opt)
     losses, sizes = [], []
     for it in range(1, 121):
         terms = T.training_iteration(m, it, s, gt, scene_extent=5.0)
@@ -379,7 +371,7 @@ def test_views_exchange_path_matches_fused_path(active_sh):
     kernel's (accum 1e-5 relative, denom / max radii exact)."""
     T = _T()
     sc, cam, s = _render_case(P=5000, W=160, H=120, seed=4)
-    raw = raw_from_scene(sc)
+    raw = G.raw_from_scene(sc)
     gt = torch.rand(3, 120, 160, device="cuda", generator=torch.Generator("cuda").manual_seed(2))
     mf = T.FlatGaussianModel(raw, 3, spatial_lr_scale=5.0)
     mv = T.FlatGaussianModel(raw, 3, spatial_lr_scale=5.0)
