@@ -1575,6 +1575,30 @@ int gs_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
     });
 }
 
+int gs_sparse_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int nseg,
+                        const long long* seg_end, const double* lr, const long long* step, int P, const int* radii,
+                        double beta1, double beta2, double eps, void* stream) {
+    return guarded([&]() -> int {
+        if (nseg < 1 || nseg > 8) throw GsError("gs_sparse_adam_step: 1..8 segments");
+        for (int i = 0; i < nseg; i++)
+            if (step[i] < 0 || (i > 0 && seg_end[i] < seg_end[i - 1]))
+                throw GsError("gs_sparse_adam_step: bad segments");
+        if (P < 0 || n < 0 || seg_end[0] < 0 || seg_end[nseg - 1] > n)
+            throw GsError("gs_sparse_adam_step: bad sizes");
+        if (P == 0 || n == 0) return 0;
+        for (int i = 0; i < nseg; i++)
+            if ((seg_end[i] - (i > 0 ? seg_end[i - 1] : 0)) % P != 0)
+                throw GsError("gs_sparse_adam_step: every segment must hold P whole rows");
+        if (!radii) throw GsError("gs_sparse_adam_step: radii is null");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        launch_sparse_adam(params, grads, exp_avg, exp_avg_sq, nseg, seg_end, lr, step, P, radii, beta1, beta2, eps, s);
+        stage_check(false, s, "sparse_adam");
+        return 0;
+    });
+}
+
+long long gs_sparse_adam_rows_per_pass(void) { return sparse_adam_rows_per_pass(); }
+
 int gs_densify_stats(int P, const int* radii, const float* grad_means2D, int grad_stride, float* xyz_gradient_accum,
                      float* denom, float* max_radii2D, void* stream) {
     return guarded([&]() -> int {

@@ -274,6 +274,12 @@ void launch_l1_ssim(const float* img, const float* gt, int C, int H, int W, floa
 // torch.optim.Adam step over a flat buffer with per-segment learning rates.
 void launch_adam(float* p, const float* g, float* m, float* v, long long N, int nseg, const long long* seg_end,
                  const double* lr, const long long* step, double beta1, double beta2, double eps, hipStream_t s);
+// Sparse Adam (upstream's --optimizer_type sparse_adam): only the rows with radii > 0, no bias correction.
+// sparse_adam_rows_per_pass: the launch cap in rows (one grid pass; more rows take the grid-stride loop).
+void launch_sparse_adam(float* p, const float* g, float* m, float* v, int nseg, const long long* seg_end,
+                        const double* lr, const long long* step, int P, const int* radii, double beta1, double beta2,
+                        double eps, hipStream_t s);
+long long sparse_adam_rows_per_pass();
 // train.py:111-113 densification statistics for the visible Gaussians.
 void launch_densify_stats(int P, const int* radii, const float* grad_means2D, int g_stride, float* accum,
                           float* denom, float* max_radii, hipStream_t s);

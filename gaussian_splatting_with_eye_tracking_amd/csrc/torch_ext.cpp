@@ -18,6 +18,7 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <limits>
 #include <optional>
 #include <string>
 #include <tuple>
@@ -1087,6 +1088,35 @@ void AdamStep(Tensor& params, const Tensor& grads, Tensor& exp_avg, Tensor& exp_
           "adam_step");
 }
 
+// Sparse Adam over the same flat buffers: only the rows with radii > 0 (one row per Gaussian in every segment).
+void SparseAdamStep(Tensor& params, const Tensor& grads, Tensor& exp_avg, Tensor& exp_avg_sq,
+                    const std::vector<int64_t>& seg_end, const std::vector<double>& lr, const std::vector<int64_t>& step,
+                    const Tensor& radii, double beta1, double beta2, double eps) {
+    for (const Tensor* t : std::initializer_list<const Tensor*>{&params, &grads, &exp_avg, &exp_avg_sq}) {
+        require_device(*t, "adam buffer");
+        TORCH_CHECK(t->is_contiguous() && t->numel() == params.numel(), "adam buffers: contiguous, same size");
+    }
+    TORCH_CHECK(seg_end.size() == lr.size() && step.size() == lr.size() && !seg_end.empty() && seg_end.back() == params.numel(),
+                "adam segments must cover the buffer");
+    TORCH_CHECK(radii.is_cuda() && radii.device() == params.device() && radii.scalar_type() == torch::kInt32 &&
+                    radii.dim() == 1 && radii.is_contiguous(),
+                "radii: int32 contiguous one-dimensional tensor on the buffers' HIP device");
+    const int64_t P = radii.numel();
+    TORCH_CHECK(P <= std::numeric_limits<int>::max(), "radii: too many rows");
+    int64_t lo = 0;
+    for (int64_t end : seg_end) {
+        TORCH_CHECK(P > 0 ? (end - lo) % P == 0 : end == lo, "sparse adam: every segment must hold radii.numel() whole rows");
+        lo = end;
+    }
+    const at::OptionalDeviceGuard guard(device_of(params));
+    std::vector<long long> ends(seg_end.begin(), seg_end.end()), steps(step.begin(), step.end());
+    check(gs_sparse_adam_step(params.data_ptr<float>(), grads.data_ptr<float>(), exp_avg.data_ptr<float>(),
+                              exp_avg_sq.data_ptr<float>(), params.numel(), (int)ends.size(), ends.data(), lr.data(),
+                              steps.data(), (int)P, P > 0 ? radii.data_ptr<int>() : nullptr, beta1, beta2, eps,
+                              stream_of(params)),
+          "sparse_adam_step");
+}
+
 // train.py:111-113: in-place statistics update (accum / denom [P, 1], max_radii [P]).
 void DensifyStats(const Tensor& radii, const Tensor& grad_means2D, Tensor& accum, Tensor& denom, Tensor& max_radii) {
     const int64_t P = radii.size(0);
@@ -1214,6 +1244,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("parse_buffers", &ParseBuffers);
     m.def("l1_ssim_loss", &L1SsimLoss);
     m.def("adam_step", &AdamStep);
+    m.def("sparse_adam_step", &SparseAdamStep);
+    m.def("sparse_adam_rows_per_pass", []() { return (int64_t)gs_sparse_adam_rows_per_pass(); });
     m.def("densify_stats", &DensifyStats);
     m.def("activate", &Activate);
     m.def("activation_backward", &ActivationBackward);

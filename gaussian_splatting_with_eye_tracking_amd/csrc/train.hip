@@ -2,11 +2,13 @@
 // rasterizer, as single-pass element-wise kernels on gfx950:
 //   * adam_kernel: torch.optim.Adam over the flat parameter buffer (all six
 //     param groups in one launch);
+//   * sparse_adam_kernel: the upstream trainer's sparse Adam, the same flat
+//     buffers, only the Gaussians visible in the view;
 //   * densify_stats_kernel: the densification statistics of train.py:111-113
 //     / scene/gaussian_model.py:405-407 (max screen radius, accumulated
 //     ||dL/dmeans2D[:2]||, view count), one pass instead of torch's
 //     gather / norm / scatter chain.
-// Both are HBM-bound; they touch each byte once.
+// All are HBM-bound; they touch each byte once.
 #include <algorithm>
 #include <cmath>
 
@@ -72,6 +74,112 @@ void launch_adam(float* p, const float* g, float* m, float* v, long long N, int 
     const int blocks = (int)std::min<long long>((N + 255) / 256, 256LL * 64);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, N, seg, (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), (float)eps);
+}
+
+// ---------------------------------------------------------- sparse Adam ---
+// The upstream trainer's --optimizer_type sparse_adam (its rasterizer's
+// adamUpdate): only the Gaussians visible in the view (radii > 0, the
+// contract of densify_stats_kernel below) are updated, with no bias
+// correction; every other row keeps p, m, v and its gradient is not read.
+// Per element of a visible row of an active segment, each operation rounded
+// on its own (-ffp-contract=off, nothing written as an fma):
+//   m = b1 * m + (1 - b1) * g
+//   v = b2 * v + ((1 - b2) * g) * g
+//   p = p + (-lr * m) / (sqrt(v) + eps)
+// Segment s holds P rows of width[s] floats.  Work split: one wave takes 64
+// consecutive rows through every segment.  It reads their 64 radii once
+// (4 P bytes in all), ballots them into a 64-bit row mask and skips the
+// chunk when the mask is empty.  Within a segment the chunk's rows are one
+// contiguous run of 64 * width floats, swept 64 floats (256 B) per step with
+// lane = element, so the accesses to visible rows are wave-contiguous dwords
+// at any segment alignment; a lane whose element lies in an invisible row is
+// masked off, a step with no visible lane issues no memory instruction, and
+// the memory pipeline fetches only the 128-B lines a live lane touches.
+// The row of a lane's element advances by (64 / width, 64 % width) per step,
+// so the loop has no division.  HBM traffic: 28 B per element of a visible
+// row (rounded up to lines) + 4 B per Gaussian.
+constexpr int kSparseAdamMaxBlocks = 2048;  // 256 CUs x 8 blocks; 4 waves (256 rows) per block
+constexpr long long kSparseAdamRowsPerPass = (long long)kSparseAdamMaxBlocks * 256;
+
+struct SparseAdamSegments {
+    int n;                 // number of segments (<= 8)
+    long long start[8];    // offset of each segment's first row
+    long long width[8];    // floats per row
+    int step_rows[8];      // 64 / width and
+    long long step_rem[8]; // 64 % width: how (row, column) of a lane's element move per 64-float step
+    float neg_lr[8];       // -(float)lr
+    int active[8];
+};
+
+__global__ void __launch_bounds__(256) sparse_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, int P,
+                                                          const int* __restrict__ radii, SparseAdamSegments seg,
+                                                          float b1, float one_minus_b1, float b2, float one_minus_b2,
+                                                          float eps) {
+    const int lane = threadIdx.x & 63;
+    const long long n_chunks = ((long long)P + 63) / 64;
+    const long long wave_stride = (long long)gridDim.x * 4;
+    for (long long chunk = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); chunk < n_chunks; chunk += wave_stride) {
+        const long long row0 = chunk * 64;
+        const int r = row0 + lane < P ? radii[row0 + lane] : 0;
+        const unsigned long long mask = __ballot(r > 0);  // bit k: row row0 + k is visible (rows past P: 0)
+        if (mask == 0) continue;
+        const long long rows = P - row0 < 64 ? P - row0 : 64;
+        for (int s = 0; s < seg.n; s++) {
+            const long long w = seg.width[s];
+            if (!seg.active[s] || w == 0) continue;
+            const long long base = seg.start[s] + row0 * w;
+            const long long len = rows * w;
+            const int step_rows = seg.step_rows[s];
+            const long long step_rem = seg.step_rem[s];
+            const int wl = w < 64 ? (int)w : 64;  // lane < 64: lane / w and lane % w in 32 bits
+            int row = lane / wl;                  // row (within the chunk) and
+            long long rem = lane % wl;            // column of this lane's element
+            const float neg_lr = seg.neg_lr[s];
+            for (long long e = lane; e - lane < len; e += 64) {
+                if (e < len && ((mask >> row) & 1)) {
+                    const long long i = base + e;
+                    const float gi = g[i];
+                    const float mi = b1 * m[i] + one_minus_b1 * gi;
+                    const float vi = b2 * v[i] + (one_minus_b2 * gi) * gi;
+                    p[i] = p[i] + (neg_lr * mi) / (sqrtf(vi) + eps);
+                    m[i] = mi;
+                    v[i] = vi;
+                }
+                row += step_rows;
+                rem += step_rem;
+                if (rem >= w) {
+                    rem -= w;
+                    row++;
+                }
+            }
+        }
+    }
+}
+
+long long sparse_adam_rows_per_pass() { return kSparseAdamRowsPerPass; }
+
+void launch_sparse_adam(float* p, const float* g, float* m, float* v, int nseg, const long long* seg_end,
+                        const double* lr, const long long* step, int P, const int* radii, double beta1, double beta2,
+                        double eps, hipStream_t s) {
+    if (P <= 0) return;
+    SparseAdamSegments seg{};
+    seg.n = nseg;
+    bool any = false;
+    for (int i = 0; i < nseg; i++) {
+        seg.start[i] = i > 0 ? seg_end[i - 1] : 0;
+        seg.width[i] = (seg_end[i] - seg.start[i]) / P;
+        seg.step_rows[i] = seg.width[i] > 0 ? (int)(64 / seg.width[i]) : 0;
+        seg.step_rem[i] = seg.width[i] > 0 ? 64 % seg.width[i] : 0;
+        seg.neg_lr[i] = -(float)lr[i];
+        seg.active[i] = step[i] > 0;
+        any = any || (seg.active[i] && seg.width[i] > 0);
+    }
+    if (!any) return;
+    const float b1 = (float)beta1, b2 = (float)beta2;
+    const int blocks = (int)std::min<long long>(((long long)P + 255) / 256, kSparseAdamMaxBlocks);
+    hipLaunchKernelGGL(sparse_adam_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, P, radii, seg, b1, 1.0f - b1, b2,
+                       1.0f - b2, (float)eps);
 }
 
 // ----------------------------------------------- densification statistics ---

@@ -15,6 +15,10 @@ scene/gaussian_model.py:149-407, laid out for one MI355X:
   over all groups, with per-group step counts so a group whose tensor was
   just replaced (densification, opacity reset) is skipped exactly as torch
   skips a parameter whose .grad is None;
+* OptimizationParams.optimizer_type = "sparse_adam" (the upstream trainer's
+  --optimizer_type) replaces that step by upstream's sparse Adam: one HIP
+  launch that updates only the Gaussians with radii > 0 in the view, without
+  bias correction, and leaves every other parameter and moment untouched;
 * the densification statistics (train.py:111-113) are one HIP launch;
 * the loss is the fused L1 + D-SSIM kernel (losses.py, csrc/loss.hip);
 * densify_and_prune / reset_opacity (:210-404) are rare (every 100 / 3000
@@ -46,6 +50,7 @@ from .rasterization import (GaussianRasterizationSettings, GaussianRasterizer, n
 GROUPS: Tuple[str, ...] = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
 BETAS = (0.9, 0.999)
 EPS = 1e-15
+OPTIMIZER_TYPES: Tuple[str, ...] = ("default", "sparse_adam")
 
 
 @dataclass
@@ -67,6 +72,7 @@ class OptimizationParams:
     densify_from_iter: int = 500
     densify_until_iter: int = 15_000
     densify_grad_threshold: float = 0.0002
+    optimizer_type: str = "default"  # upstream's --optimizer_type: "default" | "sparse_adam"
 
 
 def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
@@ -120,6 +126,8 @@ class FlatGaussianModel:
         self.active_sh_degree = 0
         self.spatial_lr_scale = float(spatial_lr_scale)
         self.opt = opt or OptimizationParams()
+        if self.opt.optimizer_type not in OPTIMIZER_TYPES:
+            raise ValueError(f"optimizer_type must be one of {OPTIMIZER_TYPES}, got {self.opt.optimizer_type!r}")
         self.percent_dense = self.opt.percent_dense
         dev = torch.device(device) if device is not None else raw["xyz"].device
         self.device = dev
@@ -230,8 +238,14 @@ class FlatGaussianModel:
         for g in GROUPS:
             self.has_grad[g] = True
 
-    def optimizer_step(self) -> None:
-        """torch.optim.Adam.step() over the groups that have a gradient."""
+    def optimizer_step(self, radii: Optional[torch.Tensor] = None) -> None:
+        """torch.optim.Adam.step() over the groups that have a gradient.  With
+        optimizer_type "sparse_adam" (upstream's SparseGaussianAdam) the step
+        is the rasterizer's adamUpdate instead: only the Gaussians with
+        radii > 0 are updated, without bias correction, and every other row
+        keeps its parameters and moments.  When no group has a gradient (the
+        step right after densify_and_prune, where `radii` still has the old
+        length) nothing is launched and `radii` is not looked at."""
         if self.P == 0:
             return
         steps = []
@@ -241,6 +255,14 @@ class FlatGaussianModel:
                 steps.append(self.steps[g])
             else:
                 steps.append(0)
+        if self.opt.optimizer_type == "sparse_adam":
+            if not any(steps):
+                return
+            if radii is None:
+                raise ValueError("optimizer_type 'sparse_adam' needs the view's radii: optimizer_step(radii)")
+            _C.sparse_adam_step(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.seg_end,
+                                [float(self.lr[g]) for g in GROUPS], steps, radii, BETAS[0], BETAS[1], EPS)
+            return
         _C.adam_step(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.seg_end,
                      [float(self.lr[g]) for g in GROUPS], steps, BETAS[0], BETAS[1], EPS)
 
@@ -441,6 +463,19 @@ def reduce_densification_stats(model: FlatGaussianModel, group=None) -> None:
         dist.all_reduce(model.max_radii2D, op=dist.ReduceOp.MAX, group=group)
 
 
+def reduce_visibility(radii: torch.Tensor, group=None) -> torch.Tensor:
+    """The sparse step's mask with more than one rank: every rank applies the
+    same summed gradient, so the rows to update are those visible in any
+    rank's view -- the element-wise maximum of the ranks' radii (visible iff
+    radii > 0), whichever exchange produced the gradients.  `radii` itself at
+    world size 1, a MAX all-reduced clone otherwise."""
+    if _world(group) == 1:
+        return radii
+    out = radii.clone()
+    dist.all_reduce(out, op=dist.ReduceOp.MAX, group=group)
+    return out
+
+
 def forward_backward(model: FlatGaussianModel, iteration: int, settings: GaussianRasterizationSettings,
                      gt_image: torch.Tensor, group=None, fused: bool = True, exchange: str = "views"):
     """train.py:76-93 + the backward: learning-rate schedule, SH degree step,
@@ -489,7 +524,10 @@ def post_backward(model: FlatGaussianModel, iteration: int, pkg, scene_extent: f
         if iteration % o.opacity_reset_interval == 0 or (white_background and iteration == o.densify_from_iter):
             model.reset_opacity()
     if iteration < o.iterations:
-        model.optimizer_step()
+        if o.optimizer_type == "sparse_adam" and any(model.has_grad.values()):
+            model.optimizer_step(reduce_visibility(pkg["radii"], group))
+        else:
+            model.optimizer_step()
         model.zero_grad(memset=not fused)
 
 

@@ -466,6 +466,28 @@ int gs_adam_step(float* params, const float* grads, float* exp_avg, float* exp_a
                  const long long* seg_end, const double* lr, const long long* step, double beta1, double beta2, double eps,
                  void* stream);
 
+/* One sparse Adam step, the upstream trainer's --optimizer_type sparse_adam
+ * (its rasterizer's adamUpdate): over the same flat buffers and segments as
+ * gs_adam_step, where segment i holds P rows of (seg_end[i] - seg_end[i-1]) / P
+ * floats (0 is legal) and radii[P] (int32, device) is the view's radii.  Only
+ * the rows with radii > 0 of the segments with step[i] > 0 are updated; every
+ * other row keeps params, exp_avg and exp_avg_sq bit for bit and its gradient
+ * is not read.  Per element, in float32, every operation rounded on its own,
+ * with b1 = (float)beta1, b2 = (float)beta2:
+ *   m = b1 * m + (1 - b1) * g
+ *   v = b2 * v + ((1 - b2) * g) * g
+ *   p = p + (-(float)lr[i] * m) / (sqrtf(v) + (float)eps)
+ * There is no bias correction: step[i] only says whether segment i is active.
+ * Errors (nothing is launched): nseg outside 1..8, a negative step, unordered
+ * seg_end, seg_end[nseg-1] > n, a segment length that is not a multiple of P,
+ * radii null with P > 0.  P == 0 or n == 0 launches nothing. */
+int gs_sparse_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, int nseg,
+                        const long long* seg_end, const double* lr, const long long* step, int P, const int* radii,
+                        double beta1, double beta2, double eps, void* stream);
+/* Rows one launch of gs_sparse_adam_step covers in a single grid pass (its
+ * launch cap); a larger P is swept by the kernel's grid-stride loop. */
+long long gs_sparse_adam_rows_per_pass(void);
+
 /* Densification statistics of train.py:111-113 and
  * scene/gaussian_model.py:405-407 for the Gaussians with radii > 0:
  * max_radii2D = max(max_radii2D, radii), xyz_gradient_accum +=
