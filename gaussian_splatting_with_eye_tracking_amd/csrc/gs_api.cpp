@@ -54,14 +54,14 @@ struct GsError : std::runtime_error {
 
 // ---- optional per-stage timing (gs_profile_*): hipEvents recorded on the
 // launch stream around each stage; elapsed times are harvested lazily.
-constexpr int kStages = 15;
+constexpr int kStages = 16;
 const char* kStageNames[kStages] = {"preprocess", "tile_scan",    "duplicate",   "sort_tiles",
                                     "render",     "render_bwd",   "bwd_gauss",   "amr_levels",
                                     "amr_render", "amr_interp",   "knn",         "zero_accum",
-                                    "count_tiles", "multiview_bwd", "amr_lists"};
+                                    "count_tiles", "multiview_bwd", "amr_lists",  "sh_colour"};
 enum Stage {
     kPre, kScan, kDup, kSort, kRender, kRenderBwd, kBwdGauss, kAmrLevels, kAmrRender, kAmrInterp, kKnn, kZero, kCount,
-    kMultiView, kAmrLists
+    kMultiView, kAmrLists, kShColour
 };
 struct Profiler {
     bool on = false;
@@ -522,12 +522,83 @@ int rendered_count(int hint, char* geom, int P, const char* binning, hipStream_t
     return K;
 }
 
+// ---- the forked base forward (set_tuning("fwd_fork")) --------
+// 1 (default): the preprocess runs as its geometry-only form on the caller's
+// stream and sh_colour_kernel on a side stream, beside the tile binning, which
+// reads none of the colour kernel's products; the blend is the first kernel
+// that does.  0: one fused preprocess on the caller's stream.
+int g_fwd_fork = 1;
+
+// One side stream and two timing-disabled events per (host thread, device),
+// created on first use and kept for the process's life, like mirror_words() /
+// copy_done_event().  The stream is non-blocking: a blocking one would
+// serialise with the legacy null stream (torch's default stream) implicitly,
+// and the fork would overlap nothing.  Default priority: the lowest one
+// measured slower (profiles/fwd_fork_ab.json).
+struct ForkLane {
+    hipStream_t side = nullptr;
+    hipEvent_t forked = nullptr;  // E1, completed by the geometry kernel's dispatch on the caller's stream
+    hipEvent_t joined = nullptr;  // E2, completed by the colour kernel's dispatch on the side stream
+    int cus = 0;                  // compute units of the device
+};
+ForkLane& fork_lane() {
+    thread_local std::vector<ForkLane> per_device;
+    int dev = 0;
+    GS_HIP(hipGetDevice(&dev));
+    if ((int)per_device.size() <= dev) per_device.resize(dev + 1);
+    ForkLane& l = per_device[dev];
+    if (!l.forked) GS_HIP(hipEventCreateWithFlags(&l.forked, hipEventDisableTiming));
+    if (!l.joined) GS_HIP(hipEventCreateWithFlags(&l.joined, hipEventDisableTiming));
+    if (!l.side) GS_HIP(hipStreamCreateWithFlags(&l.side, hipStreamNonBlocking));
+    if (!l.cus) GS_HIP(hipDeviceGetAttribute(&l.cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return l;
+}
+// The colour kernel's grid: one workgroup per compute unit, each walking its
+// share of the 256-Gaussian chunks, but never more than 16 chunks each.  A
+// full grid takes all the HBM bandwidth it can get and the latency-bound
+// binning kernels beside it slow down by more than the overlap saves
+// (band_stage 25 -> 45 us at config 2); the capped grid spreads the same
+// bytes over more of the binning's duration.  The 16-chunk bound keeps the
+// kernel inside that duration as P grows (config 4: a full grid again).
+int colour_blocks(const ForkLane& l, int P) {
+    const int nchunks = (P + 255) / 256;
+    return std::max(l.cus, (nchunks + 15) / 16);
+}
+
+// The join of one forked forward: the caller's stream waits for E2.  join() is
+// called right before the blend's launch; the destructor makes the same wait
+// on every other exit between fork and join (an exception: the prefiltered
+// error behind the K read-back, a failing resize callback, a HIP error), so
+// whatever the caller enqueues on its stream afterwards -- a free and reuse of
+// the geometry buffer included -- is ordered behind the colour kernel.
+struct ForkJoin {
+    hipStream_t s = nullptr, side = nullptr;
+    hipEvent_t joined = nullptr;
+    bool armed = false, recorded = false;
+    ForkJoin() = default;
+    ForkJoin(const ForkJoin&) = delete;
+    ForkJoin& operator=(const ForkJoin&) = delete;
+    hipError_t wait() {
+        armed = false;
+        if (!recorded) {  // (the fork itself failed half way)
+            const hipError_t e = hipEventRecord(joined, side);
+            if (e != hipSuccess) return e;
+        }
+        return hipStreamWaitEvent(s, joined, 0);
+    }
+    void join() { if (armed) GS_HIP(wait()); }
+    ~ForkJoin() { if (armed) GS_HIP_NOTHROW(wait()); }
+};
+
 // preprocess -> tile scan -> (K read-back) -> duplicate -> per-tile sort.
 // `before_k`: work that needs the scan but not K, enqueued behind the K copy
 // and run while the host waits for it.
+// `fork` (base forwards): where a forked call leaves its join (above); the
+// caller joins before the first reader of rgb / clamped / drgb.
 Binned preprocess_and_bin(const ForwardIn& in, const gs_buffer& geometry, const gs_buffer& binning,
                           const gs_buffer& image, int* radii, int tile, bool debug, hipStream_t s,
-                          const std::function<void(Binned&)>& before_k = nullptr, int fused_sort_max = 0) {
+                          const std::function<void(Binned&)>& before_k = nullptr, int fused_sort_max = 0,
+                          ForkJoin* fork = nullptr) {
     Binned r;
     const int W = in.width, H = in.height;
     const int gx = (W + tile - 1) / tile, gy = (H + tile - 1) / tile;
@@ -555,7 +626,27 @@ Binned preprocess_and_bin(const ForwardIn& in, const gs_buffer& geometry, const 
         pa.zero_words = r.img.tile_count;
         pa.zero_n = kBinSlots * r.T;
     }
-    { StageTimer _t(kPre, s); launch_preprocess(pa, r.g, r.radii, lds_bin ? nullptr : r.img.tile_count, s); }
+    // Forked (fwd_fork): SH colours, base tiles (the AMR blend row mixes
+    // geometry and colour), not in debug mode (its per-stage synchronise
+    // watches one stream), and something to bin.
+    const bool forked = fork && g_fwd_fork != 0 && tile == 16 && in.colors_precomp == nullptr && !debug && r.T > 0;
+    pa.split_colour = forked ? 1 : 0;
+    if (!forked) {
+        StageTimer _t(kPre, s);
+        launch_preprocess(pa, r.g, r.radii, lds_bin ? nullptr : r.img.tile_count, s);
+    } else {
+        ForkLane& lane = fork_lane();
+        // E1 and E2 are completed by the two kernels' own dispatches
+        // (hipExtLaunchKernelGGL): a marker packet behind the geometry kernel
+        // would idle the caller's queue for ~6 us before count_tiles.
+        // E1: radii, and every input the caller's stream produced, are ready.
+        { StageTimer _t(kPre, s); launch_preprocess(pa, r.g, r.radii, lds_bin ? nullptr : r.img.tile_count, s, lane.forked); }
+        GS_HIP(hipStreamWaitEvent(lane.side, lane.forked, 0));
+        fork->s = s; fork->side = lane.side; fork->joined = lane.joined;
+        fork->armed = true;  // from here on every exit joins
+        { StageTimer _t(kShColour, lane.side); launch_sh_colour(pa, r.g, r.radii, lane.side, colour_blocks(lane, in.P), lane.joined); }
+        fork->recorded = true;  // E2
+    }
     stage_check(debug, s, "preprocess");
     if (lds_bin) { StageTimer _t(kCount, s); launch_count_tiles(in.P, r.g, r.radii, W, H, tile, r.img, s); }
     stage_check(debug, s, "count_tiles");
@@ -655,8 +746,10 @@ int base_forward_impl(const ForwardIn& in, const gs_buffer& geometry, const gs_b
         }
         return 0;
     }
-    Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s);
+    ForkJoin fork;  // (declared first: its destructor joins on every exit below)
+    Binned r = preprocess_and_bin(in, geometry, binning, image, radii, 16, debug != 0, s, nullptr, 0, &fork);
     const float* feats = in.colors_precomp ? in.colors_precomp : r.g.rgb;
+    fork.join();  // the blend is the first reader of rgb
     bool zeroed;
     {
         StageTimer _t(kRender, s, true);
@@ -1663,6 +1756,9 @@ const TuningKey kTuning[] = {
     {"hdr_mirror", &g_hdr_mirror, [](int v) { g_hdr_mirror = v == 0 ? 0 : 2; }},
     // speculative duplicate before the K read-back (base forward)
     {"spec_dup", &g_spec_dup, [](int v) { g_spec_dup = v; }},
+    // 0: one fused preprocess; 1: the SH colour kernel on a side stream beside
+    // the binning (base forward, default)
+    {"fwd_fork", &g_fwd_fork, [](int v) { g_fwd_fork = v != 0; }},
     // 0: the SGPR-weight FMA convolution; 1: matrix cores (default)
     {"ritnet_mfma", &g_ritnet_mfma, set_ritnet_mfma},
 };

@@ -48,11 +48,23 @@ struct PreprocessArgs {
     // the Mip-Splatting 2D filter: the recorded opacity is the input's times
     // sqrt(max(0.000025, det cov2D / det (cov2D + 0.3 I))) (base tiles only)
     int antialiasing = 0;
+    // the forked forward (gs_api.cpp fwd_fork): launch_preprocess runs the
+    // geometry-only form although the colours come from SHs, and
+    // launch_sh_colour writes rgb / clamped / drgb from the radii it left
+    // (in the struct's tail padding: the kernels' argument layout is unchanged)
+    int split_colour = 0;
 };
 
 // base/cr/forward.cu:155-256 (+ the tile histogram the binning needs).
+// done (optional): an event the kernel's own dispatch completes (hipExtLaunchKernelGGL:
+// no marker packet behind the kernel).
 void launch_preprocess(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count,
-                       hipStream_t s);
+                       hipStream_t s, hipEvent_t done = nullptr);
+// The SH colour half of a split_colour preprocess (forward.cu:240-247), for
+// the Gaussians whose radii the geometry half left > 0: the fused kernel's bits.
+// max_blocks > 0 caps the grid; done as above.
+void launch_sh_colour(const PreprocessArgs& a, const GeomView& g, const int* radii, hipStream_t s,
+                      int max_blocks = 0, hipEvent_t done = nullptr);
 // base/cr/rasterizer_impl.cu:54-66
 void launch_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                          bool* present, hipStream_t s);

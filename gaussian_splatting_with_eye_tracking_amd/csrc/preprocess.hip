@@ -13,6 +13,8 @@
 //   * no FMA contraction (file compiled with -ffp-contract=off): depth,
 //     means2D and radius are bit-identical to the oracle, which makes the
 //     tile keys bit-exact.
+#include <hip/hip_ext.h>
+
 #include <algorithm>
 
 #include "gs_blend.cuh"
@@ -355,7 +357,8 @@ __global__ void __launch_bounds__(kPpThreads) preprocess_kernel(PreprocessArgs a
     for (int i = idx; i < a.zero_n; i += (int)(gridDim.x * blockDim.x)) a.zero_words[i] = 0u;
     // whether the backward may take d(rgb)/d(dir) from g.drgb (every visible
     // Gaussian's row is written below)
-    if (idx == 0) g.hdr[kHdrDrgb] = (kHasSH && a.store_drgb) ? 1u : 0u;
+    // (split_colour: sh_colour_kernel writes them behind this launch)
+    if (idx == 0) g.hdr[kHdrDrgb] = ((kHasSH || a.split_colour) && a.store_drgb) ? 1u : 0u;
     // whether the recorded opacities carry the antialiasing coefficient (the
     // per-Gaussian backward refuses a call whose flag says otherwise)
     if (idx == 0) g.hdr[kHdrAntialias] = kAA ? 1u : 0u;
@@ -418,8 +421,18 @@ __global__ void __launch_bounds__(kPpThreads) preprocess_kernel(PreprocessArgs a
 }
 
 template <bool A, bool B, bool C>
-static void launch_pp(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count, hipStream_t s) {
+static void launch_pp(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count, hipStream_t s,
+                      hipEvent_t done) {
     const int blocks = (a.P + kPpThreads - 1) / kPpThreads;
+    if (done) {  // (the forked forward: the dispatch completes `done`)
+        if (a.antialiasing && a.block == 16)
+            hipExtLaunchKernelGGL((preprocess_kernel<A, B, C, A && B, true>), dim3(blocks), dim3(kPpThreads), 0, s,
+                                  nullptr, done, 0, a, g, radii, tile_count);
+        else
+            hipExtLaunchKernelGGL((preprocess_kernel<A, B, C, A && B>), dim3(blocks), dim3(kPpThreads), 0, s, nullptr,
+                                  done, 0, a, g, radii, tile_count);
+        return;
+    }
     // (the AMR preprocess, 32-px tiles, has no antialiased form: gs_api.cpp refuses the flag there)
     if (a.antialiasing && a.block == 16)
         hipLaunchKernelGGL((preprocess_kernel<A, B, C, A && B, true>), dim3(blocks), dim3(kPpThreads), 0, s, a, g,
@@ -430,23 +443,193 @@ static void launch_pp(const PreprocessArgs& a, const GeomView& g, int* radii, ui
 }
 
 void launch_preprocess(const PreprocessArgs& a, const GeomView& g, int* radii, uint32_t* tile_count,
-                       hipStream_t s) {
+                       hipStream_t s, hipEvent_t done) {
     if (a.P == 0) return;
-    const bool has_sh = a.colors_precomp == nullptr;
+    const bool has_sh = a.colors_precomp == nullptr && !a.split_colour;
     const bool sh16 = has_sh && a.M == 16;
     const bool covp = a.cov3D_precomp != nullptr;
     if (has_sh) {
         if (sh16) {
-            if (covp) launch_pp<true, true, true>(a, g, radii, tile_count, s);
-            else launch_pp<true, true, false>(a, g, radii, tile_count, s);
+            if (covp) launch_pp<true, true, true>(a, g, radii, tile_count, s, done);
+            else launch_pp<true, true, false>(a, g, radii, tile_count, s, done);
         } else {
-            if (covp) launch_pp<true, false, true>(a, g, radii, tile_count, s);
-            else launch_pp<true, false, false>(a, g, radii, tile_count, s);
+            if (covp) launch_pp<true, false, true>(a, g, radii, tile_count, s, done);
+            else launch_pp<true, false, false>(a, g, radii, tile_count, s, done);
         }
     } else {
-        if (covp) launch_pp<false, false, true>(a, g, radii, tile_count, s);
-        else launch_pp<false, false, false>(a, g, radii, tile_count, s);
+        if (covp) launch_pp<false, false, true>(a, g, radii, tile_count, s, done);
+        else launch_pp<false, false, false>(a, g, radii, tile_count, s, done);
     }
+}
+
+// sh_colour_kernel's pieces: preprocess_kernel's kDma steps as functions (that
+// kernel keeps its own text, so its code generation stays what was measured).
+// Wave w of a workgroup copies rows [64 w, 64 w + 64) of the block's Gaussians:
+// lane l writes LDS piece p = l + 64 i = (row p / 13, 16-B piece p % 13 of it).
+__device__ __forceinline__ void sh_rows_dma(const PreprocessArgs& a, float* s_sh, int chunk) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t row0 = (size_t)chunk * kPpThreads + 64 * w;
+    const float* src = a.shs + row0 * 48;
+    float* dst = s_sh + 64 * kShStride * w;
+    constexpr int kPieces = kShStride / 4;  // 13
+#pragma unroll
+    for (int i = 0; i < kPieces; i++) {
+        const int p = 64 * i + lane, r = p / kPieces, j = p - kPieces * r;
+        if (j < 12 && row0 + (size_t)r < (size_t)a.P)
+            __builtin_amdgcn_global_load_lds(src + 48 * r + 4 * j, dst + 256 * i, 16, 0, 2);  // (nt)
+    }
+}
+
+// The thread's coefficients from its LDS row, once this wave's LDS-DMA rows
+// have landed.
+__device__ __forceinline__ void read_sh_row(const PreprocessArgs& a, const float* sh_row, float (&shc)[16][3]) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA rows have landed
+    const int ncoef = min((a.D + 1) * (a.D + 1), a.M);
+    // twelve b128 reads of the padded row (conflict-free, kShStride)
+    // (the empty asm keeps each piece one 128-bit register tuple, so the
+    // compiler does not split the reads into conflicting b32 / b64 ones)
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    float v[48];
+#pragma unroll
+    for (int i = 0; i < 12; i++) {
+        f4v t = reinterpret_cast<const f4v*>(sh_row)[i];
+        asm volatile("" : "+v"(t));
+        v[4 * i] = t.x; v[4 * i + 1] = t.y; v[4 * i + 2] = t.z; v[4 * i + 3] = t.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) shc[k][ch] = k < ncoef ? v[3 * k + ch] : 0.f;
+}
+
+// A wave's staged records (LDS rows wl, Gaussians [wrow0, wrow0 + nrow)) as
+// wave-contiguous 16-B stores: 64 d(rgb)/d(dir) rows x three 16-B pieces ...
+__device__ __forceinline__ void store_wave_drgb(const GeomView& g, const float* wl, int wrow0, int nrow, int lane) {
+    float4* out = reinterpret_cast<float4*>(g.drgb) + 3 * (size_t)wrow0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const int c = lane + 64 * i;
+        if (c < 3 * nrow) {
+            const float4 v = *reinterpret_cast<const float4*>(wl + kShStride * (c / 3) + 4 * (c % 3));
+            typedef float f4v __attribute__((ext_vector_type(4)));
+            __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f4v*>(out + c));
+        }
+    }
+}
+
+// ... and 64 x 3 rgb floats = 48 pieces of 4.
+__device__ __forceinline__ void store_wave_rgb(const GeomView& g, const float* wl, int wrow0, int nrow, int lane) {
+    const int nf = 3 * nrow;
+    if (4 * lane < nf) {
+        float v4[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int f = min(4 * lane + e, nf - 1);
+            v4[e] = wl[kShStride * (f / 3) + 12 + f % 3];
+        }
+        float* out = g.rgb + 3 * (size_t)wrow0 + 4 * lane;
+        if (4 * lane + 4 <= nf) {
+            *reinterpret_cast<float4*>(out) = make_float4(v4[0], v4[1], v4[2], v4[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 3; e++)
+                if (4 * lane + e < nf) out[e] = v4[e];
+        }
+    }
+}
+
+// The colour of one Gaussian the geometry kernel kept: pp_gaussian's kHasSH
+// block on the same operands (the same expressions under the same flags, so
+// the records are the fused kernel's bits).
+template <bool kSH16>
+__device__ __forceinline__ void colour_thread(const PreprocessArgs& a, const GeomView& g, int idx, float mx, float my,
+                                              float mz, const float* sh_row, float* stage) {
+    float shc[16][3];
+    if constexpr (kSH16) read_sh_row(a, sh_row, shc);
+    else load_sh<false>(a.D, a.M, a.shs + (size_t)idx * a.M * 3, shc);
+    // computeColorFromSH: dir = normalize(mean - campos)
+    float dx = mx - a.cam_pos[0], dy = my - a.cam_pos[1], dz = mz - a.cam_pos[2];
+    const float len = sqrtf(dot3(dx, dy, dz, dx, dy, dz));
+    dx = dx / len; dy = dy / len; dz = dz / len;
+    uint8_t cbits;
+    const float3 rgb = eval_sh_color(a.D, shc, dx, dy, dz, cbits);
+    if (a.store_drgb) {
+        float dx3[3], dy3[3], dz3[3];
+        sh_ddir(a.D, shc, dx, dy, dz, dx3, dy3, dz3);
+        float4* row = stage ? reinterpret_cast<float4*>(stage)
+                            : reinterpret_cast<float4*>(g.drgb) + 3 * (size_t)idx;
+        row[0] = make_float4(dx3[0], dx3[1], dx3[2], dy3[0]);
+        row[1] = make_float4(dy3[1], dy3[2], dz3[0], dz3[1]);
+        row[2] = make_float4(dz3[2], 0.f, 0.f, 0.f);
+    }
+    if (stage) {
+        *reinterpret_cast<float4*>(stage + 12) = make_float4(rgb.x, rgb.y, rgb.z, 0.f);
+    } else {
+        g.rgb[3 * idx + 0] = rgb.x;
+        g.rgb[3 * idx + 1] = rgb.y;
+        g.rgb[3 * idx + 2] = rgb.z;
+    }
+    g.clamped[idx] = cbits;
+}
+
+// The SH colour path of the preprocess as a kernel of its own, launched behind
+// the geometry-only preprocess_kernel<false, ...> on a second stream so that it
+// runs beside the tile binning (which reads none of its products): rgb,
+// clamped and the drgb rows of the Gaussians with radii > 0.  kSH16: the SH
+// rows through the same LDS-DMA and the records through the same staged wave
+// stores as the fused kernel; otherwise load_sh and per-thread stores.  Rows
+// of culled Gaussians carry stale words, as the fused kernel's do.
+template <bool kSH16>
+__global__ void __launch_bounds__(kPpThreads) sh_colour_kernel(PreprocessArgs a, GeomView g,
+                                                               const int* __restrict__ radii, int nchunks) {
+    __shared__ __attribute__((aligned(16))) float s_sh[kSH16 ? kPpThreads * kShStride : 1];
+    // chunk = 256 consecutive Gaussians; a capped grid walks the chunks (each
+    // wave owns its 64 LDS rows from one chunk to the next: no workgroup barrier)
+    for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const int idx = chunk * kPpThreads + threadIdx.x;
+        // the per-thread loads first: their wait then leaves the LDS-DMA in flight
+        const int ci = min(idx, a.P - 1);
+        const int radius = radii[ci];
+        const float mx = a.means3D[3 * ci + 0], my = a.means3D[3 * ci + 1], mz = a.means3D[3 * ci + 2];
+        if constexpr (kSH16) {
+            sh_rows_dma(a, s_sh, chunk);
+            float* row = s_sh + kShStride * threadIdx.x;
+            // every lane of a wave takes part in its coalesced record stores below
+            const int wrow0 = chunk * kPpThreads + (int)(threadIdx.x & ~63u);
+            if (wrow0 >= a.P) return;  // wave-uniform (the last chunk's tail)
+            if (idx < a.P && radius > 0) colour_thread<true>(a, g, idx, mx, my, mz, row, row);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int lane = threadIdx.x & 63;
+            const float* wl = s_sh + kShStride * (threadIdx.x & ~63u);
+            const int nrow = min(64, a.P - wrow0);
+            if (a.store_drgb) store_wave_drgb(g, wl, wrow0, nrow, lane);
+            store_wave_rgb(g, wl, wrow0, nrow, lane);
+            // the next chunk's LDS-DMA overwrites the rows: every lane's reads
+            // of them (and a culled wave's still pending DMA) are done first
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            if (idx < a.P && radius > 0) colour_thread<false>(a, g, idx, mx, my, mz, nullptr, nullptr);
+        }
+    }
+}
+
+// max_blocks > 0 caps the grid (the kernel then walks the chunks: gs_api.cpp
+// colour_blocks says why); done: an event the dispatch itself completes (no
+// marker packet behind the kernel).
+void launch_sh_colour(const PreprocessArgs& a, const GeomView& g, const int* radii, hipStream_t s, int max_blocks,
+                      hipEvent_t done) {
+    if (a.P == 0) return;
+    const int nchunks = (a.P + kPpThreads - 1) / kPpThreads;
+    const int blocks = max_blocks > 0 ? std::min(nchunks, max_blocks) : nchunks;
+    if (a.M == 16)
+        hipExtLaunchKernelGGL(sh_colour_kernel<true>, dim3(blocks), dim3(kPpThreads), 0, s, nullptr, done, 0, a, g,
+                              radii, nchunks);
+    else
+        hipExtLaunchKernelGGL(sh_colour_kernel<false>, dim3(blocks), dim3(kPpThreads), 0, s, nullptr, done, 0, a, g,
+                              radii, nchunks);
 }
 
 // base/cr/rasterizer_impl.cu:54-66 (checkFrustum)

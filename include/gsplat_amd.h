@@ -606,7 +606,9 @@ void gs_profile_set_mask(unsigned mask);
  * Gaussians whose alpha >= 1/255 ellipse misses a 16x4 row group, the
  * default; 0 only to verify that the cull is exact), "hdr_mirror" (2 = the
  * polled K read-back, the default; 0 = copy + event), "spec_dup" (1 = the
- * speculative duplicate before the K read-back, the default), "ritnet_mfma"
+ * speculative duplicate before the K read-back, the default), "fwd_fork"
+ * (1 = the base forward's SH colour kernel on an internal side stream beside
+ * the tile binning, the default; 0 = one fused preprocess), "ritnet_mfma"
  * (1 = matrix-core convolutions, the default; 0 = SGPR-weight FMA kernel).
  * Returns 0, or -1 for an unknown key. */
 int gs_set_tuning(const char* key, int value);
