@@ -36,11 +36,12 @@ def _load_native():
 _C = _load_native()
 
 from .rasterization import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: E402
-                            rasterize_gaussians, rasterize_gaussians_aux, _RasterizeGaussians,
-                            set_deterministic)
+                            rasterize_gaussians, rasterize_gaussians_aux, rasterize_gaussians_invdepth,
+                            _RasterizeGaussians, set_deterministic)
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "_RasterizeGaussians",
-           "_C", "native_library_paths", "set_deterministic", "rasterize_gaussians_aux"]
+           "_C", "native_library_paths", "set_deterministic", "rasterize_gaussians_aux",
+           "rasterize_gaussians_invdepth"]
 
 
 def native_library_paths() -> list[str]:

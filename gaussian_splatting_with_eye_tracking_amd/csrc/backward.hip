@@ -196,7 +196,7 @@ void launch_render_backward_deterministic(int W, int H, int P, int R, const Imag
 // walk of the tile lists, ten sums per Gaussian into g.grad_accum.
 void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                                 const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
-                                const float* dL_dalpha, hipStream_t s) {
+                                const float* dL_dalpha, hipStream_t s, bool inverse) {
     const int gx = (W + 15) / 16, gy = (H + 15) / 16;
     if (gx == 0 || gy == 0) return;
     const DispatchEvents ev = take_dispatch_events();
@@ -204,31 +204,43 @@ void launch_render_backward_aux(int W, int H, const ImageView& img, const Binnin
     p.depths = g.depths;
     p.dL_ddepth = dL_ddepth;
     p.dL_dalpha = dL_dalpha;
-    hipExtLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kAux>, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0,
-                          p);
+    if (inverse)
+        hipExtLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kAuxInv>, dim3(gx * gy), dim3(64), 0, s, ev.start,
+                              ev.stop, 0, p);
+    else
+        hipExtLaunchKernelGGL(render_bwd_rows_kernel<BwdRows::kAux>, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop,
+                              0, p);
 }
 
 // The depth map's direct term on the means: z = V[2] x + V[6] y + V[10] z +
 // V[14] of the flat viewmatrix (transformPoint4x3), so dL_dmeans3D[i] +=
 // dL/dz_i (V[2], V[6], V[10]) with dL/dz_i the row's float kAuxDz.  Runs
 // after backward_gaussians_kernel, which wrote every dL_dmeans3D element.
+// inv_depths (the inverse-depth map, null otherwise): the row's float is
+// dL/df_i for f_i = 1 / z_i, and dL/dz_i = -f_i^2 dL/df_i with f_i the
+// forward's quotient (inv_depth); nothing is divided for an invisible Gaussian.
 __global__ void __launch_bounds__(256) aux_depth_to_means_kernel(int P, const int* __restrict__ radii,
                                                                  const float* __restrict__ grad_accum,
                                                                  const float* __restrict__ viewmatrix,
-                                                                 float* __restrict__ dL_dmean3D) {
+                                                                 float* __restrict__ dL_dmean3D,
+                                                                 const float* __restrict__ inv_depths) {
     const int idx = (int)(blockIdx.x * 256u + threadIdx.x);
     if (idx >= P || radii[idx] <= 0) return;
-    const float dz = grad_accum[(size_t)idx * kGradRow + kAuxDz];
+    float dz = grad_accum[(size_t)idx * kGradRow + kAuxDz];
+    if (inv_depths) {
+        const float f = inv_depth(inv_depths[idx]);
+        dz = -(f * f) * dz;
+    }
     dL_dmean3D[3 * idx + 0] += dz * viewmatrix[2];
     dL_dmean3D[3 * idx + 1] += dz * viewmatrix[6];
     dL_dmean3D[3 * idx + 2] += dz * viewmatrix[10];
 }
 
 void launch_aux_depth_to_means(int P, const GeomView& g, const int* radii, const float* viewmatrix,
-                               float* dL_dmean3D, hipStream_t s) {
+                               float* dL_dmean3D, hipStream_t s, bool inverse) {
     if (P <= 0) return;
     hipLaunchKernelGGL(aux_depth_to_means_kernel, dim3(((unsigned)P + 255u) / 256u), dim3(256), 0, s, P, radii,
-                       g.grad_accum, viewmatrix, dL_dmean3D);
+                       g.grad_accum, viewmatrix, dL_dmean3D, inverse ? g.depths : nullptr);
 }
 
 // The foveated (AMR) blend backward: 32-px tile ranges, one wave per

@@ -729,12 +729,15 @@ namespace {
 // The base forward: preprocess + binning + blend, and with `aux` one replay of
 // the tile lists for the depth and alpha maps.  The plain and the aux entry
 // make the same launches in the same order up to the replay, so the image, the
-// radii and the three buffers are the same bits either way.
+// radii and the three buffers are the same bits either way.  `inverse`: the
+// replay blends 1 / z, and out_depth is the inverse-depth map.
 int base_forward_impl(const ForwardIn& in, const gs_buffer& geometry, const gs_buffer& binning,
                       const gs_buffer& image, float* out_color, int* radii, bool aux, float* out_depth,
-                      float* out_alpha, int debug, void* stream, const char* who) {
+                      float* out_alpha, int debug, void* stream, const char* who, bool inverse = false) {
     const int P = in.P, width = in.width, height = in.height;
-    if (aux && (!out_depth || !out_alpha)) throw GsError(std::string(who) + ": out_depth / out_alpha is NULL");
+    if (aux && (!out_depth || !out_alpha))
+        throw GsError(std::string(who) +
+                      (inverse ? ": out_invdepth / out_alpha is NULL" : ": out_depth / out_alpha is NULL"));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (P <= 0) {
         if (aux) {  // nothing blended: zero maps
@@ -764,7 +767,7 @@ int base_forward_impl(const ForwardIn& in, const gs_buffer& geometry, const gs_b
     if (zeroed) set_accum_clean(r.g.grad_accum, true);
     stage_check(debug != 0, s, "render");
     if (aux) {
-        launch_render_forward_aux(width, height, r.img, r.b, r.g, out_depth, out_alpha, s);
+        launch_render_forward_aux(width, height, r.img, r.b, r.g, out_depth, out_alpha, s, inverse);
         stage_check(debug != 0, s, "render_aux");
     }
     return r.K;
@@ -824,6 +827,25 @@ int gs_rasterizer_forward_ex(gs_buffer geometry, gs_buffer binning, gs_buffer im
     });
 }
 
+// gs_rasterizer_forward_ex with the inverse-depth map in the depth map's place.
+int gs_rasterizer_forward_invdepth(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                                   const float* background, int width, int height, const float* means3D,
+                                   const float* shs, const float* colors_precomp, const float* opacities,
+                                   const float* scales, float scale_modifier, const float* rotations,
+                                   const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                   const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                   int antialiasing, float* out_color, int* radii, float* out_invdepth,
+                                   float* out_alpha, int debug, void* stream) {
+    ForwardIn in = forward_in(false, P, D, M, background, width, height, means3D, shs, colors_precomp, opacities,
+                              scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos,
+                              tan_fovx, tan_fovy, prefiltered);
+    in.antialiasing = antialiasing != 0;
+    return guarded([&]() -> int {
+        return base_forward_impl(in, geometry, binning, image, out_color, radii, true, out_invdepth, out_alpha, debug,
+                                 stream, "gs_rasterizer_forward_invdepth", true);
+    });
+}
+
 namespace {
 // The deterministic backward's scratch: one row of kDetRow floats per sorted
 // instance (gs_backward_deterministic_scratch_bytes).
@@ -860,7 +882,9 @@ struct BackwardCall {
     DetScratch det;
     // gs_rasterizer_backward_aux: the depth / alpha maps' cotangents (either
     // may be null; dL_dpix too there)
-    bool aux = false;
+    // (gs_rasterizer_backward_invdepth: `inverse`, and dL_ddepth is the
+    // inverse-depth map's cotangent)
+    bool aux = false, inverse = false;
     const float *dL_ddepth = nullptr, *dL_dalpha = nullptr;
     int debug = 0;
     hipStream_t s = nullptr;
@@ -928,7 +952,7 @@ int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
         if (c.R > 0) {
             StageTimer _t(kRenderBwd, s, true);
             launch_render_backward_aux(c.width, c.height, v.img, v.b, g, colors, c.background, c.dL_dpix, c.dL_ddepth,
-                                       c.dL_dalpha, s);
+                                       c.dL_dalpha, s, c.inverse);
         }
     } else {
         blend_backward(c.det, c.width, c.height, a.P, c.R, v.img, v.b, g, a.radii, colors, c.background, c.dL_dpix,
@@ -960,7 +984,7 @@ int rasterizer_backward_impl(int amr_mode, const BackwardCall& c) {
                                 "and its opacities (gs_rasterizer_backward_ex)");
     }
     if (c.aux && c.dL_ddepth && c.R > 0) {  // the depth map's direct term on the means
-        launch_aux_depth_to_means(a.P, g, a.radii, a.viewmatrix, a.dL_dmean3D, s);
+        launch_aux_depth_to_means(a.P, g, a.radii, a.viewmatrix, a.dL_dmean3D, s, c.inverse);
         stage_check(c.debug != 0, s, "aux_depth_to_means");
     }
     return 0;
@@ -1123,6 +1147,32 @@ int gs_amr_rasterizer_backward(int P, int D, int M, int R, const float* backgrou
     });
 }
 
+namespace {
+// What the two superset backwards add to backward_call's arguments: the
+// antialiasing flag with the forward's opacities, the maps' cotangents
+// (dL_dmap: the depth map's, or with `inverse` the inverse-depth map's), the
+// deterministic blend.
+int superset_backward(const char* who, bool inverse, BackwardCall c, const float* opacities, int antialiasing,
+                      const float* dL_dmap, const float* dL_dalpha, int deterministic, char* scratch,
+                      size_t scratch_bytes) {
+    c.a.opacities = opacities;
+    c.a.antialiasing = antialiasing != 0;
+    if (dL_dmap || dL_dalpha) {
+        if (deterministic)
+            throw GsError(std::string(who) + ": the deterministic backward takes no " +
+                          (inverse ? "inverse-depth" : "depth") + " / alpha cotangents");
+        c.aux = true;
+        c.inverse = inverse;
+        c.dL_ddepth = dL_dmap;
+        c.dL_dalpha = dL_dalpha;
+    } else if (!c.dL_dpix && c.a.P > 0) {
+        throw GsError(std::string(who) + ": every cotangent is NULL");
+    }
+    if (deterministic) c.det = DetScratch{true, scratch, scratch_bytes};
+    return rasterizer_backward_impl(0, c);
+}
+}  // namespace
+
 // The superset backward: the antialiasing flag with the forward's opacities,
 // the maps' cotangents, the deterministic blend.
 int gs_rasterizer_backward_ex(int P, int D, int M, int R, const float* background, int width, int height,
@@ -1136,24 +1186,37 @@ int gs_rasterizer_backward_ex(int P, int D, int M, int R, const float* backgroun
                               float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
                               int deterministic, char* scratch, size_t scratch_bytes, int debug, void* stream) {
     return guarded([&]() -> int {
-        BackwardCall c = backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
-                                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
-                                       tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, img_buffer, dL_dpix,
-                                       dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                                       dL_dscale, dL_drot, debug, stream);
-        c.a.opacities = opacities;
-        c.a.antialiasing = antialiasing != 0;
-        if (dL_ddepth || dL_dalpha) {
-            if (deterministic)
-                throw GsError("gs_rasterizer_backward_ex: the deterministic backward takes no depth / alpha cotangents");
-            c.aux = true;
-            c.dL_ddepth = dL_ddepth;
-            c.dL_dalpha = dL_dalpha;
-        } else if (!dL_dpix && P > 0) {
-            throw GsError("gs_rasterizer_backward_ex: every cotangent is NULL");
-        }
-        if (deterministic) c.det = DetScratch{true, scratch, scratch_bytes};
-        return rasterizer_backward_impl(0, c);
+        return superset_backward(
+            "gs_rasterizer_backward_ex", false,
+            backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+                          dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream),
+            opacities, antialiasing, dL_ddepth, dL_dalpha, deterministic, scratch, scratch_bytes);
+    });
+}
+
+// gs_rasterizer_backward_ex with the inverse-depth map's cotangent in the
+// depth map's place.
+int gs_rasterizer_backward_invdepth(int P, int D, int M, int R, const float* background, int width, int height,
+                                    const float* means3D, const float* shs, const float* colors_precomp,
+                                    const float* opacities, const float* scales, float scale_modifier,
+                                    const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                    const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                    const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                    const float* dL_dpix, const float* dL_dinvdepth, const float* dL_dalpha,
+                                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                    float* dL_drot, int antialiasing, int deterministic, char* scratch,
+                                    size_t scratch_bytes, int debug, void* stream) {
+    return guarded([&]() -> int {
+        return superset_backward(
+            "gs_rasterizer_backward_invdepth", true,
+            backward_call(P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                          rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                          geom_buffer, binning_buffer, img_buffer, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+                          dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, stream),
+            opacities, antialiasing, dL_dinvdepth, dL_dalpha, deterministic, scratch, scratch_bytes);
     });
 }
 
@@ -1650,6 +1713,19 @@ int gs_l1_ssim_loss(const float* image, const float* gt, int C, int H, int W, fl
         char* ws = call_resize(workspace, l1_ssim_workspace_bytes(C, H, W), "loss workspace");
         launch_l1_ssim(image, gt, C, H, W, lambda_dssim, grad, out3, reinterpret_cast<float*>(ws), s);
         stage_check(false, s, "l1_ssim");
+        return 0;
+    });
+}
+
+int gs_depth_l1_loss(const float* invdepth, const float* target, const float* mask, int H, int W, float weight,
+                     float* grad, float* out1, gs_buffer workspace, void* stream) {
+    return guarded([&]() -> int {
+        if (H <= 0 || W <= 0) return 0;
+        if (!invdepth || !target || !grad || !out1) throw GsError("gs_depth_l1_loss: a NULL argument");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        char* ws = call_resize(workspace, depth_l1_workspace_bytes(H, W), "depth loss workspace");
+        launch_depth_l1(invdepth, target, mask, H, W, weight, grad, out1, reinterpret_cast<double*>(ws), s);
+        stage_check(false, s, "depth_l1");
         return 0;
     });
 }

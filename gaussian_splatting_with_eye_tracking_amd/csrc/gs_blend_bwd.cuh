@@ -450,8 +450,8 @@ __global__ void __launch_bounds__(64, 4) render_bwd_kernel(BlendBwdParams p) {
     }
 }
 
-// What the rows form is run for.  kAmr, kDet and kAux each extend the base.
-enum class BwdRows { kBase, kAmr, kDet, kAux };
+// What the rows form is run for.  kAmr, kDet and kAux each extend the base; kAuxInv is kAux on 1 / z.
+enum class BwdRows { kBase, kAmr, kDet, kAux, kAuxInv };
 
 // The rows form: the predicate visit, full sums by transposition into LDS accumulator rows, one flush pass per batch
 // -- one 64-B atomic row per (tile, Gaussian).
@@ -467,11 +467,16 @@ enum class BwdRows { kBase, kAmr, kDet, kAux };
 // background (0, 0) and cotangents dL_ddepth / dL_dalpha (either may be null, as dL_dpixels then: zeros) replayed in
 // the same walk -- dL/dalpha of every pair gains their terms, and a tenth per-Gaussian sum dL/dz = sum alpha T
 // dL_ddepth goes to float kAuxDz of the Gaussian's grad_accum row (LDS rows of 10).
+// kAuxInv (the inverse-depth / alpha maps' backward): kAux with the record's z replaced by f = 1 / z (inv_depth, the
+// forward's quotient) -- features (f, 1), p.dL_ddepth the inverse-depth map's cotangent, and float kAuxDz takes
+// dL/df = sum alpha T dL_dinvdepth.  (An instantiation of its own: kAux keeps its code, and the parameter block
+// its layout.)
 // (a template parameter: run-time branches cost the base kernel 12 %)
 template <BwdRows kMode>
 __global__ void __launch_bounds__(64, 4) render_bwd_rows_kernel(BlendBwdParams p) {
 #pragma clang fp contract(fast)
-    constexpr bool kAMR = kMode == BwdRows::kAmr, kDet = kMode == BwdRows::kDet, kAux = kMode == BwdRows::kAux;
+    constexpr bool kAMR = kMode == BwdRows::kAmr, kDet = kMode == BwdRows::kDet;
+    constexpr bool kInv = kMode == BwdRows::kAuxInv, kAux = kMode == BwdRows::kAux || kInv;
     constexpr int kRow = kAux ? kAccRow + 1 : kAccRow;  // LDS accumulator row of this mode
     constexpr int kB = kBwdBatch;
     __shared__ uint32_t s_id[2][kB];  // double-buffered: the next batch's ids land while this one flushes
@@ -544,11 +549,11 @@ __global__ void __launch_bounds__(64, 4) render_bwd_rows_kernel(BlendBwdParams p
     const int ia = (kAux && comp == kAuxDz) ? kAuxDz : comp < 3 ? comp : comp == 8 ? 3 : comp < 5 ? 4 : comp + 1;
 
     NextRecord nr;
-    float nz = 0.f;  // kAux: the Gaussian's view-space depth, carried with the record
+    float nz = 0.f;  // kAux: the Gaussian's view-space depth (kAuxInv: its inverse), carried with the record
     if (tid < min(kB, m)) {
         nr.load_id(p, codes, range.x + m - 1 - tid);
         nr.gather(p);
-        if constexpr (kAux) nz = p.depths[nr.id];
+        if constexpr (kAux) nz = kInv ? inv_depth(p.depths[nr.id]) : p.depths[nr.id];
         s_id[0][tid] = nr.id;
     }
     int par = 0;
@@ -651,7 +656,7 @@ __global__ void __launch_bounds__(64, 4) render_bwd_rows_kernel(BlendBwdParams p
         if (has_next) {  // gathers for the next batch, ahead of the flush atomics
             s_id[par ^ 1][tid] = nr.id;
             nr.gather(p);
-            if constexpr (kAux) nz = p.depths[nr.id];
+            if constexpr (kAux) nz = kInv ? inv_depth(p.depths[nr.id]) : p.depths[nr.id];
         }
         // Flush: 16 lanes per Gaussian row, 4 rows per wave instruction (one 64-B memory-side atomic request per
         // (tile, Gaussian)).  (A full unroll lets the scheduler hoist all 64 LDS reads: 163 VGPRs.)

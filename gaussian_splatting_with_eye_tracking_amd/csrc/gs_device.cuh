@@ -34,6 +34,24 @@ __device__ __forceinline__ float4 ldg4(const float4* p) {
     }
 }
 
+// 1 / z as one correctly rounded float division, in every translation unit:
+// the expansion the compiler gives `1.0f / z` under the exact contract, spelt
+// out, because backward.hip is compiled with -freciprocal-math and would turn
+// the plain quotient into a bare v_rcp_f32 (1 ulp).  The inverse-depth map's
+// forward, its backward and its chain onto the means all take f = 1 / z from
+// here, so they agree to the bit.
+__device__ __forceinline__ float inv_depth(float z) {
+    bool vd, vn;
+    const float ds = __builtin_amdgcn_div_scalef(1.0f, z, false, &vd);  // the scaled denominator
+    const float ns = __builtin_amdgcn_div_scalef(1.0f, z, true, &vn);   // the scaled numerator
+    const float r0 = __builtin_amdgcn_rcpf(ds);
+    const float r = __builtin_fmaf(__builtin_fmaf(-ds, r0, 1.0f), r0, r0);
+    const float q0 = ns * r;
+    const float q1 = __builtin_fmaf(__builtin_fmaf(-ds, q0, ns), r, q0);
+    const float rem = __builtin_fmaf(-ds, q1, ns);
+    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(rem, r, q1, vn), z, 1.0f);
+}
+
 // base/cr/auxiliary.h:22-39
 __device__ constexpr float SH_C0 = 0.28209479177387814f;
 __device__ constexpr float SH_C1 = 0.4886025119029199f;

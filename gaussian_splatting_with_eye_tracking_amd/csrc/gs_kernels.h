@@ -123,18 +123,22 @@ bool launch_render_forward(int W, int H, const ImageView& img, const BinningView
 // The depth / alpha maps of the forward just rendered into img (its n_contrib
 // and the sorted lists): out_depth = sum z alpha T, out_alpha = sum alpha T,
 // [H][W] each, every pixel written (render.hip render_aux_fwd_kernel).
+// inverse: out_depth = sum (1 / z) alpha T instead, the inverse-depth map.
 void launch_render_forward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
-                               float* out_depth, float* out_alpha, hipStream_t s);
+                               float* out_depth, float* out_alpha, hipStream_t s, bool inverse = false);
 // Their backward: the blend backward over five channels (colour, z, 1) into
 // g.grad_accum -- floats 0..8 the totals of the nine sums, float kAuxDz
 // dL/dz (gs_blend_bwd.cuh render_bwd_rows_kernel kAux).  Any cotangent may be null.
+// inverse (kAuxInv): the channels are (colour, 1 / z, 1), dL_ddepth is the
+// inverse-depth map's cotangent and float kAuxDz takes dL/df, f = 1 / z.
 void launch_render_backward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
                                 const float* colors, const float* bg, const float* dL_dpix, const float* dL_ddepth,
-                                const float* dL_dalpha, hipStream_t s);
+                                const float* dL_dalpha, hipStream_t s, bool inverse = false);
 // dL_dmean3D += dL/dz (V[2], V[6], V[10]) for the visible Gaussians, after
-// launch_backward_gaussians has written dL_dmean3D.
+// launch_backward_gaussians has written dL_dmean3D.  inverse: the row holds
+// dL/df, and dL/dz = -f^2 dL/df with f = 1 / z of g.depths.
 void launch_aux_depth_to_means(int P, const GeomView& g, const int* radii, const float* viewmatrix,
-                               float* dL_dmean3D, hipStream_t s);
+                               float* dL_dmean3D, hipStream_t s, bool inverse = false);
 // Tuning knobs (gs_set_tuning): the default or one fallback each.
 void set_forward_variant(int v);
 void set_backward_variant(int v);
@@ -283,6 +287,10 @@ void radix_sort_pairs_u32(int n, const uint32_t* keys_in, uint32_t* keys_out, co
 size_t l1_ssim_workspace_bytes(int C, int H, int W);
 void launch_l1_ssim(const float* img, const float* gt, int C, int H, int W, float lambda, float* grad, float* out3,
                     float* workspace, hipStream_t s);
+// The depth term (loss.hip): out1[0] = mean |(x - t) mask|, grad = weight * sgn * mask / (H W); mask null: ones.
+size_t depth_l1_workspace_bytes(int H, int W);
+void launch_depth_l1(const float* x, const float* t, const float* mask, int H, int W, float weight, float* grad,
+                     float* out1, double* workspace, hipStream_t s);
 // torch.optim.Adam step over a flat buffer with per-segment learning rates.
 void launch_adam(float* p, const float* g, float* m, float* v, long long N, int nseg, const long long* seg_end,
                  const double* lr, const long long* step, double beta1, double beta2, double eps, hipStream_t s);

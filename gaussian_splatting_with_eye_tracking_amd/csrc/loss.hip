@@ -231,4 +231,75 @@ void launch_l1_ssim(const float* img, const float* gt, int C, int H, int W, floa
     hipLaunchKernelGGL(l1_ssim_reduce_kernel, dim3(1), dim3(256), 0, s, nblk, workspace, lambda, 1.0 / n, out3);
 }
 
+// ------------------------------------------------ depth regularisation ---
+// The depth term of the upstream trainer: out[0] = mean over H W of
+// |(x - t) m| (x the rendered inverse depth, t the target, m the mask; null:
+// ones) and grad = weight * d out[0] / dx = weight * sgn * m / (H W), float32
+// in that order.  sgn is the sign of (x - t) m decided by comparisons -- x
+// against t, times the sign of m -- never from a rounded (or flushed)
+// difference.  One elementwise pass, per-thread and per-workgroup partial sums
+// in float64 in a fixed order, then one workgroup sums the partials: the same
+// bits on every call.
+namespace {
+constexpr int kDepthThreads = 256;
+constexpr int kDepthMaxBlocks = 1024;
+}  // namespace
+
+__global__ void __launch_bounds__(kDepthThreads) depth_l1_kernel(const float* __restrict__ x,
+                                                                 const float* __restrict__ t,
+                                                                 const float* __restrict__ mask, long long n,
+                                                                 float weight, float n_f, float* __restrict__ grad,
+                                                                 double* __restrict__ partials) {
+    __shared__ double red[kDepthThreads];
+    double acc = 0.0;
+    const long long stride = (long long)gridDim.x * kDepthThreads;
+    for (long long i = (long long)blockIdx.x * kDepthThreads + threadIdx.x; i < n; i += stride) {
+        const float xv = x[i], tv = t[i], mv = mask ? mask[i] : 1.0f;
+        acc += fabs(((double)xv - (double)tv) * (double)mv);  // (the difference and the product are exact in float64)
+        const float sd = xv > tv ? 1.0f : (xv < tv ? -1.0f : 0.0f);
+        const float sm = mv > 0.0f ? 1.0f : (mv < 0.0f ? -1.0f : 0.0f);
+        grad[i] = ((weight * (sd * sm)) * mv) / n_f;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = kDepthThreads / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(kDepthThreads) depth_l1_reduce_kernel(int nblk, const double* __restrict__ partials,
+                                                                        double inv_n, float* __restrict__ out) {
+    __shared__ double red[kDepthThreads];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += kDepthThreads) a += partials[i];
+    red[threadIdx.x] = a;
+    __syncthreads();
+    for (int off = kDepthThreads / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)(red[0] * inv_n);
+}
+
+static int depth_l1_blocks(int H, int W) {
+    const long long n = (long long)H * W;
+    const long long b = (n + kDepthThreads - 1) / kDepthThreads;
+    return (int)(b < 1 ? 1 : (b > kDepthMaxBlocks ? kDepthMaxBlocks : b));
+}
+
+size_t depth_l1_workspace_bytes(int H, int W) { return sizeof(double) * (size_t)depth_l1_blocks(H, W); }
+
+void launch_depth_l1(const float* x, const float* t, const float* mask, int H, int W, float weight, float* grad,
+                     float* out1, double* workspace, hipStream_t s) {
+    if (H <= 0 || W <= 0) return;
+    const long long n = (long long)H * W;
+    const int nblk = depth_l1_blocks(H, W);
+    hipLaunchKernelGGL(depth_l1_kernel, dim3(nblk), dim3(kDepthThreads), 0, s, x, t, mask, n, weight, (float)n, grad,
+                       workspace);
+    hipLaunchKernelGGL(depth_l1_reduce_kernel, dim3(1), dim3(kDepthThreads), 0, s, nblk, workspace, 1.0 / (double)n,
+                       out1);
+}
+
 }  // namespace gsamd

@@ -169,6 +169,10 @@ bool launch_render_forward(int W, int H, const ImageView& img, const BinningView
 // batches of 64 entries (x, y, z + the scaled conic), the row-group cull and
 // each row group's max n_contrib as wave-uniform skips.  Every pixel of the
 // image is written (zeros where nothing contributes).
+// kInv (gs_rasterizer_forward_invdepth): the third staged word is f = 1 / z
+// (inv_depth) in place of z, so out_depth is the inverse-depth map sum f_i
+// alpha_i T_i; nothing else in the walk differs.
+template <bool kInv>
 __global__ void __launch_bounds__(64) render_aux_fwd_kernel(int W, int H, const uint32_t* __restrict__ ranges,
                                                             const uint32_t* __restrict__ point_list,
                                                             const float2* __restrict__ means2D,
@@ -178,7 +182,7 @@ __global__ void __launch_bounds__(64) render_aux_fwd_kernel(int W, int H, const 
                                                             float* __restrict__ out_depth,
                                                             float* __restrict__ out_alpha, int cull, int gx) {
     constexpr int kB = 64, kPPL = 4;
-    __shared__ float4 s_a[kB];  // (x, y, z, -)
+    __shared__ float4 s_a[kB];  // (x, y, z, -); kInv: (x, y, 1 / z, -)
     __shared__ float4 s_co[kB];
     __shared__ uint64_t s_bal[4];
     const int lane = (int)threadIdx.x;
@@ -211,7 +215,7 @@ __global__ void __launch_bounds__(64) render_aux_fwd_kernel(int W, int H, const 
             const uint32_t id = point_list[range.x + b0 + lane];
             const float2 xy = means2D[id];
             const float4 co = conic_opacity[id];
-            s_a[lane] = make_float4(xy.x, xy.y, depths[id], 0.f);
+            s_a[lane] = make_float4(xy.x, xy.y, kInv ? inv_depth(depths[id]) : depths[id], 0.f);
             s_co[lane] = splat_coef(co);
             gm = cull ? splat_group_mask(xy, co, (float)ox, (float)oy, 1.0f) : 0xfu;
         }
@@ -259,14 +263,18 @@ __global__ void __launch_bounds__(64) render_aux_fwd_kernel(int W, int H, const 
 }
 
 void launch_render_forward_aux(int W, int H, const ImageView& img, const BinningView& b, const GeomView& g,
-                               float* out_depth, float* out_alpha, hipStream_t s) {
+                               float* out_depth, float* out_alpha, hipStream_t s, bool inverse) {
     const int gx = (W + 15) / 16, gy = (H + 15) / 16;
     if (gx == 0 || gy == 0) return;
     const DispatchEvents ev = take_dispatch_events();
-    hipExtLaunchKernelGGL(render_aux_fwd_kernel, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0, W, H, img.ranges,
-                          b.point_list, reinterpret_cast<const float2*>(g.means2D),
-                          reinterpret_cast<const float4*>(g.conic_opacity), g.depths, img.n_contrib, out_depth,
-                          out_alpha, g_cull, gx);
+#define GS_AUX_FWD(INV)                                                                                               \
+    hipExtLaunchKernelGGL(render_aux_fwd_kernel<INV>, dim3(gx * gy), dim3(64), 0, s, ev.start, ev.stop, 0, W, H,       \
+                          img.ranges, b.point_list, reinterpret_cast<const float2*>(g.means2D),                       \
+                          reinterpret_cast<const float4*>(g.conic_opacity), g.depths, img.n_contrib, out_depth,       \
+                          out_alpha, g_cull, gx)
+    if (inverse) GS_AUX_FWD(true);
+    else GS_AUX_FWD(false);
+#undef GS_AUX_FWD
 }
 
 // ------------------------------------------------------------------- AMR ---

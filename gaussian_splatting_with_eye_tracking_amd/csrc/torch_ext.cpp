@@ -170,23 +170,28 @@ struct ForwardCall {
     float scale_modifier, tan_fovx, tan_fovy;
     bool prefiltered, debug;
     bool antialiasing = false;  // base forwards only
+    bool inverse = false;       // with maps: the inverse-depth map in the depth map's place
     void* stream;
 };
 
-// The base forward; with `maps` also the depth and alpha maps ([1, H, W] each).
+// The base forward; with `maps` also the depth (o.inverse: inverse-depth) and
+// alpha maps ([1, H, W] each).
 Forward6 base_forward(ForwardCall& o, std::pair<Tensor, Tensor>* maps = nullptr) {
     if (maps) {
         maps->first = torch::empty({1, o.H, o.W}, o.out_color.options());
         maps->second = torch::empty({1, o.H, o.W}, o.out_color.options());
     }
-    const int rendered = gs_rasterizer_forward_ex(
+    // (the two entries share their argument list)
+    const auto forward = maps && o.inverse ? gs_rasterizer_forward_invdepth : gs_rasterizer_forward_ex;
+    const int rendered = forward(
         buf_of(o.geom), buf_of(o.binning), buf_of(o.image), o.P, o.degree, o.M, fptr(o.bg), o.W, o.H, fptr(o.means3D),
         fptr(o.sh), fptr(o.colors), fptr(o.opacity), fptr(o.scales), o.scale_modifier, fptr(o.rotations),
         fptr(o.cov3D_precomp), fptr(o.viewmatrix), fptr(o.projmatrix), fptr(o.campos), o.tan_fovx, o.tan_fovy,
         o.prefiltered, o.antialiasing, o.out_color.data_ptr<float>(), o.radii.data_ptr<int>(),
         maps ? maps->first.data_ptr<float>() : nullptr, maps ? maps->second.data_ptr<float>() : nullptr, o.debug,
         o.stream);
-    check(rendered, maps ? "rasterize_gaussians_aux" : "rasterize_gaussians");
+    check(rendered,
+          !maps ? "rasterize_gaussians" : o.inverse ? "rasterize_gaussians_invdepth" : "rasterize_gaussians_aux");
     return std::make_tuple(rendered, o.out_color, o.radii, o.geom, o.binning, o.image);
 }
 
@@ -263,8 +268,10 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
                         const Tensor& sh_in, int degree, const Tensor& campos_in, bool prefiltered, int foveaStep,
                         const Tensor& out_color_precomp_in, const Tensor& geom_pre, const Tensor& bin_pre,
                         const Tensor& img_pre, bool interpolate_image, bool debug,
-                        std::pair<Tensor, Tensor>* aux_maps = nullptr, bool antialiasing = false) {
+                        std::pair<Tensor, Tensor>* aux_maps = nullptr, bool antialiasing = false,
+                        bool inverse = false) {
     TORCH_CHECK(!(amr && antialiasing), "the AMR rasterizer has no antialiased form");
+    TORCH_CHECK(!(amr && inverse), "the AMR rasterizer has no inverse-depth form");
     if (means3D_in.ndimension() != 2 || means3D_in.size(1) != 3) {
         AT_ERROR("means3D must have dimensions (num_points, 3)");
     }
@@ -310,6 +317,7 @@ Forward6 rasterize_impl(bool amr, const Tensor& background, const Tensor& means3
     o.prefiltered = prefiltered;
     o.debug = debug;
     o.antialiasing = antialiasing;
+    o.inverse = inverse;
     o.stream = stream_of(o.means3D);
     // both forwards write every pixel (the AMR one zeros where it renders
     // nothing) and all radii (the AMR steps >= 1 write their zero radii in
@@ -335,7 +343,10 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor> RasterizeGaussians(
 }
 
 // RasterizeGaussians plus the depth and alpha maps:
-// (K, color, depth, alpha, radii, geom, binning, img).
+// (K, color, depth, alpha, radii, geom, binning, img).  kInv
+// (rasterize_gaussians_invdepth): the inverse-depth map sum (1 / z) alpha T in
+// the depth map's place.
+template <bool kInv>
 std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> RasterizeGaussiansAux(
     const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity,
     const Tensor& scales, const Tensor& rotations, const float scale_modifier, const Tensor& cov3D_precomp,
@@ -346,7 +357,8 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> Rasteriz
     std::pair<Tensor, Tensor> maps;
     Forward6 f = rasterize_impl(false, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                 cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width,
-                                sh, degree, campos, prefiltered, -1, e, e, e, e, false, debug, &maps, antialiasing);
+                                sh, degree, campos, prefiltered, -1, e, e, e, e, false, debug, &maps, antialiasing,
+                                kInv);
     return std::make_tuple(std::get<0>(f), std::get<1>(f), maps.first, maps.second, std::get<2>(f), std::get<3>(f),
                            std::get<4>(f), std::get<5>(f));
 }
@@ -414,6 +426,7 @@ struct BackwardCall {
     Tensor bg, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, sh, campos;
     Tensor dL_dout;               // [3, H, W] always: it carries H and W
     Tensor dL_ddepth, dL_dalpha;  // the aux bindings' map cotangents, [1, H, W]; empty: absent
+    bool inverse = false;         // dL_ddepth is the inverse-depth map's cotangent (the invdepth bindings)
     Tensor opacities;             // the forward's input (the antialiased backward reads it); empty: not given
     Tensor none;                  // an empty tensor, for what a call does not have
     Tensor geom, binning, image;
@@ -511,13 +524,15 @@ Grads8 BackwardImpl(BackwardCall c, const int amr_step = 0, const bool interpola
         TORCH_CHECK(!c.antialiasing || opac.numel() != 0,
                     "rasterize_gaussians_backward: antialiasing needs the forward's opacities");
         TORCH_CHECK(amr_step == 0 || !aux, "the AMR backward takes no depth / alpha cotangents");
+        TORCH_CHECK(amr_step == 0 || !c.inverse, "the AMR backward has no inverse-depth form");
         TORCH_CHECK(!(aux && t_det_backward),
-                    "rasterize_gaussians_backward_aux: the deterministic backward has no form that takes depth / "
-                    "alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
+                    c.inverse ? "rasterize_gaussians_backward_invdepth" : "rasterize_gaussians_backward_aux",
+                    ": the deterministic backward has no form that takes ", c.inverse ? "inverse-depth" : "depth",
+                    " / alpha cotangents (no deterministic aux backward is built); turn the deterministic mode off "
                     "for this call");
         require_like(opac, c.means3D, "opacities", P);
         const Tensor dd = c.dL_ddepth.contiguous(), da = c.dL_dalpha.contiguous();
-        require_like(dd, c.means3D, "dL_ddepth", (int64_t)H * W);
+        require_like(dd, c.means3D, c.inverse ? "dL_dinvdepth" : "dL_ddepth", (int64_t)H * W);
         require_like(da, c.means3D, "dL_dalpha", (int64_t)H * W);
         int rc;
         if (amr_step == 0) {
@@ -529,7 +544,9 @@ Grads8 BackwardImpl(BackwardCall c, const int amr_step = 0, const bool interpola
             // call always was.  No pixel is read, so any other call without pixels
             // hands over a non-null pointer instead and gets what it always got.
             const float* dL_dpix = c.dL_dout.numel() != 0 || c.antialiasing ? fptr(c.dL_dout) : fptr(c.means3D);
-            rc = gs_rasterizer_backward_ex(
+            // (the inverse-depth entry shares the superset entry's argument list)
+            const auto backward = c.inverse ? gs_rasterizer_backward_invdepth : gs_rasterizer_backward_ex;
+            rc = backward(
                 P, c.degree, c.M, c.R, fptr(c.bg), W, H, fptr(c.means3D), fptr(c.sh), fptr(c.colors), fptr(opac),
                 fptr(c.scales), c.scale_modifier, fptr(c.rotations), fptr(c.cov3D_precomp), fptr(c.viewmatrix),
                 fptr(c.projmatrix), fptr(c.campos), c.tan_fovx, c.tan_fovy, c.radii.data_ptr<int>(),
@@ -551,7 +568,9 @@ Grads8 BackwardImpl(BackwardCall c, const int amr_step = 0, const bool interpola
                 fptr_mut(c.dL_dmeans3D), fptr_mut(c.dL_dcov3D), fptr_mut(c.dL_dsh), fptr_mut(c.dL_dscales),
                 fptr_mut(c.dL_drotations), c.debug, c.stream);
         }
-        check(rc, amr_step ? "amr_rasterize_gaussians_backward" : "rasterize_gaussians_backward");
+        check(rc, amr_step    ? "amr_rasterize_gaussians_backward"
+                  : c.inverse ? "rasterize_gaussians_backward_invdepth"
+                              : "rasterize_gaussians_backward");
     }
     return std::make_tuple(c.dL_dmeans2D, c.dL_dcolors, c.dL_dopacity, c.dL_dmeans3D, c.dL_dcov3D, c.dL_dsh,
                            c.dL_dscales, c.dL_drotations);
@@ -592,8 +611,9 @@ Grads8 RasterizeGaussiansBackwardLean(const Tensor& background, const Tensor& me
 // dL_ddepth / dL_dalpha ([1, H, W], or empty: absent) after dL_dout_color
 // (which is [3, H, W] always: it carries H and W; zeros when the colour took
 // no part).  With both empty it is rasterize_gaussians_backward (kLean: _lean,
-// for the autograd wrapper).
-template <bool kLean>
+// for the autograd wrapper).  kInv (rasterize_gaussians_backward_invdepth,
+// _lean): dL_ddepth is the inverse-depth map's cotangent.
+template <bool kLean, bool kInv = false>
 Grads8 RasterizeGaussiansBackwardAux(const Tensor& background, const Tensor& means3D, const Tensor& radii,
                                      const Tensor& colors, const Tensor& scales, const Tensor& rotations,
                                      const float scale_modifier, const Tensor& cov3D_precomp,
@@ -609,6 +629,7 @@ Grads8 RasterizeGaussiansBackwardAux(const Tensor& background, const Tensor& mea
                                    antialiasing);
     c.dL_ddepth = dL_ddepth;
     c.dL_dalpha = dL_dalpha;
+    c.inverse = kInv;
     return BackwardImpl(std::move(c));
 }
 
@@ -1070,6 +1091,29 @@ std::tuple<Tensor, Tensor> L1SsimLoss(const Tensor& image, const Tensor& gt, dou
     return std::make_tuple(out3, grad);
 }
 
+// The depth-regularisation term (loss.hip): returns (out1 = [mean |(x - t) m|],
+// grad = weight * d out1 / d x).  mask: absent or empty means ones.
+std::tuple<Tensor, Tensor> DepthL1Loss(const Tensor& invdepth, const Tensor& target, const std::optional<Tensor>& mask,
+                                       double weight) {
+    TORCH_CHECK(invdepth.dim() >= 2, "invdepth must be [H, W] or [1, H, W]");
+    const int64_t H = invdepth.size(-2), W = invdepth.size(-1);
+    TORCH_CHECK(invdepth.numel() == H * W, "invdepth must hold one H x W map");
+    require_device(invdepth, "invdepth");
+    const at::OptionalDeviceGuard guard(device_of(invdepth));
+    const Tensor x = invdepth.contiguous(), t = target.contiguous();
+    TORCH_CHECK(t.numel() == H * W, "target has ", t.numel(), " elements, expected ", H * W);
+    require_like(t, x, "target", H * W);
+    const Tensor m = mask.has_value() ? mask->contiguous() : torch::empty({0}, x.options());
+    if (m.numel() != 0) require_like(m, x, "mask", H * W);
+    Tensor grad = torch::empty_like(x);
+    Tensor out1 = torch::empty({1}, x.options());
+    Tensor ws = torch::empty({0}, x.options().dtype(torch::kByte));
+    check(gs_depth_l1_loss(fptr(x), fptr(t), fptr(m), (int)H, (int)W, (float)weight, fptr_mut(grad),
+                           out1.data_ptr<float>(), buf_of(ws), stream_of(x)),
+          "depth_l1_loss");
+    return std::make_tuple(out1, grad);
+}
+
 // Fused Adam over flat buffers: seg_end / lr per segment (host lists).
 void AdamStep(Tensor& params, const Tensor& grads, Tensor& exp_avg, Tensor& exp_avg_sq,
               const std::vector<int64_t>& seg_end, const std::vector<double>& lr, const std::vector<int64_t>& step, double beta1,
@@ -1214,11 +1258,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians", &RasterizeGaussians, GS_FWD_ARGS);
     m.def("rasterize_gaussians_backward", &RasterizeGaussiansBackward, GS_BWD_HEAD, GS_BWD_TAIL);
     m.def("rasterize_gaussians_backward_lean", &RasterizeGaussiansBackwardLean, GS_BWD_HEAD, GS_BWD_TAIL);
-    m.def("rasterize_gaussians_aux", &RasterizeGaussiansAux, GS_FWD_ARGS);
+    m.def("rasterize_gaussians_aux", &RasterizeGaussiansAux<false>, GS_FWD_ARGS);
     m.def("rasterize_gaussians_backward_aux", &RasterizeGaussiansBackwardAux<false>, GS_BWD_HEAD,
           py::arg("dL_ddepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
     m.def("rasterize_gaussians_backward_aux_lean", &RasterizeGaussiansBackwardAux<true>, GS_BWD_HEAD,
           py::arg("dL_ddepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
+    m.def("rasterize_gaussians_invdepth", &RasterizeGaussiansAux<true>, GS_FWD_ARGS);
+    m.def("rasterize_gaussians_backward_invdepth", &RasterizeGaussiansBackwardAux<false, true>, GS_BWD_HEAD,
+          py::arg("dL_dinvdepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
+    m.def("rasterize_gaussians_backward_invdepth_lean", &RasterizeGaussiansBackwardAux<true, true>, GS_BWD_HEAD,
+          py::arg("dL_dinvdepth"), py::arg("dL_dalpha"), GS_BWD_TAIL);
 #undef GS_FWD_ARGS
 #undef GS_BWD_HEAD
 #undef GS_BWD_TAIL
@@ -1243,6 +1292,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("distCUDA2", &DistCUDA2);
     m.def("parse_buffers", &ParseBuffers);
     m.def("l1_ssim_loss", &L1SsimLoss);
+    m.def("depth_l1_loss", &DepthL1Loss, py::arg("invdepth"), py::arg("target"), py::arg("mask") = py::none(),
+          py::arg("weight") = 1.0);
     m.def("adam_step", &AdamStep);
     m.def("sparse_adam_step", &SparseAdamStep);
     m.def("sparse_adam_rows_per_pass", []() { return (int64_t)gs_sparse_adam_rows_per_pass(); });

@@ -124,6 +124,18 @@ def refuse_antialiasing(settings, who: str) -> None:
                                   "all-reduce (exchange=\"params\") or turn antialiasing off")
 
 
+def refuse_depth_target(invdepth_target, who: str, group=None, world: Optional[int] = None) -> None:
+    """The view records have no word for dL/dz, and the multi-view backward no
+    inverse-depth chain onto the means: with more than one rank (``world``;
+    default: the process group's size) a depth target cannot go through the
+    view exchange, so the request is refused.  One rank exchanges nothing."""
+    if world is None:
+        world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    if invdepth_target is not None and world > 1:
+        raise NotImplementedError(f"{who}: the view exchange carries no depth gradient; train with a depth target "
+                                  "through the gradient all-reduce (exchange=\"params\")")
+
+
 def view_record(settings, radii: torch.Tensor, geom: torch.Tensor, num_rendered: int, binning: torch.Tensor,
                 img: torch.Tensor, dL_dpix: torch.Tensor, colors_precomp: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Stage 1: the blend backward of one rendered view -> its view record."""

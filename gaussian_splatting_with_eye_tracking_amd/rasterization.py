@@ -47,6 +47,20 @@ def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, sca
                                         cov3Ds_precomp, raster_settings)
 
 
+def rasterize_gaussians_invdepth(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                 raster_settings):
+    """``rasterize_gaussians`` plus the differentiable inverse-depth and alpha
+    maps: ``(color [3,H,W], radii [P], invdepth [1,H,W], alpha [1,H,W])`` with
+    ``invdepth = sum (1 / z_i) alpha_i T_i`` (view-space z, one correctly rounded
+    float division, no background term, not normalised) and ``alpha = sum
+    alpha_i T_i`` over the colour blend's contributors: the upstream
+    rasterizer's third output, which its depth regularisation reads
+    (INTEGRATION.md §4g).  ``color`` and ``radii`` are the plain call's bits,
+    ``alpha`` is ``rasterize_gaussians_aux``'s."""
+    return _RasterizeGaussiansInvDepth.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                             cov3Ds_precomp, raster_settings)
+
+
 def _call(fn, args, debug: bool, dump: str, what: str):
     """debug mode: snapshot the arguments and re-raise (base/.../__init__.py:83-90)."""
     if not debug:
@@ -119,8 +133,8 @@ class _DeterministicScope:
 
 
 def native_forward_args(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
-    """The positional arguments of ``_C.rasterize_gaussians`` / ``_aux``: the one
-    place that knows their order."""
+    """The positional arguments of ``_C.rasterize_gaussians`` / ``_aux`` /
+    ``_invdepth``: the one place that knows their order."""
     s = settings
     return (s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, s.image_height, s.image_width, sh, s.sh_degree,
@@ -130,7 +144,8 @@ def native_forward_args(settings, means3D, sh, colors_precomp, opacities, scales
 def native_backward_args(settings, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                          radii, geomBuffer, binningBuffer, imgBuffer, num_rendered, grad_color, grad_maps=None):
     """The positional arguments of ``_C.rasterize_gaussians_backward`` / ``_lean``
-    or, with ``grad_maps = (dL_ddepth, dL_dalpha)``, of ``_aux`` / ``_aux_lean``.
+    or, with ``grad_maps = (dL_ddepth, dL_dalpha)``, of ``_aux`` / ``_aux_lean``
+    (``(dL_dinvdepth, dL_dalpha)``: of ``_invdepth`` / ``_invdepth_lean``).
     ``opacities``: the forward's input, read by the antialiased backward only."""
     s = settings
     return ((s.bg, means3D, radii, colors_precomp, scales, rotations, s.scale_modifier, cov3Ds_precomp,
@@ -140,7 +155,8 @@ def native_backward_args(settings, means3D, sh, colors_precomp, opacities, scale
 
 
 class _RasterizeBase(torch.autograd.Function):
-    """What _RasterizeGaussians and _RasterizeGaussiansAux share: the one-shot
+    """What _RasterizeGaussians, _RasterizeGaussiansAux and
+    _RasterizeGaussiansInvDepth share: the one-shot
     forward-only hint around ``apply``, the native forward with what the
     backward needs saved, and the lean native backward with its gradients put
     into input order."""
@@ -169,9 +185,10 @@ class _RasterizeBase(torch.autograd.Function):
         return outs
 
     @staticmethod
-    def native_backward(ctx, grad_out_color, grad_maps=None):
+    def native_backward(ctx, grad_out_color, grad_maps=None, inverse=False):
         s = ctx.raster_settings
-        fn = _C.rasterize_gaussians_backward_lean if grad_maps is None else _C.rasterize_gaussians_backward_aux_lean
+        fn = (_C.rasterize_gaussians_backward_lean if grad_maps is None else
+              _C.rasterize_gaussians_backward_invdepth_lean if inverse else _C.rasterize_gaussians_backward_aux_lean)
         args = native_backward_args(s, *ctx.saved_tensors, ctx.num_rendered, grad_out_color, grad_maps)
         with _DeterministicScope():
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
@@ -196,6 +213,40 @@ class _RasterizeGaussians(_RasterizeBase):
         return _RasterizeBase.native_backward(ctx, grad_out_color)
 
 
+def _maps_forward(ctx, fn, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
+    """The forward of the two classes with maps: ``fn`` is ``_C.rasterize_gaussians_aux``
+    or ``_C.rasterize_gaussians_invdepth``."""
+    color, depth, alpha, radii = _RasterizeBase.native_forward(
+        ctx, fn, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings)
+    ctx.mark_non_differentiable(radii)
+    return color, radii, depth, alpha
+
+
+def _maps_backward(ctx, grad_out_color, grad_depth, grad_alpha, inverse):
+    """Their backward (``grad_depth``: the depth map's cotangent, or with
+    ``inverse`` the inverse-depth map's)."""
+    if grad_out_color is None and grad_depth is None and grad_alpha is None:
+        return (None,) * 9
+    aux = grad_depth is not None or grad_alpha is not None
+    if aux and deterministic_requested():
+        who, what = (("rasterize_gaussians_invdepth", "inverse-depth") if inverse else
+                     ("rasterize_gaussians_aux", "depth"))
+        raise RuntimeError(
+            f"{who}: the deterministic backward has no form that takes {what} / alpha "
+            "cotangents (a deterministic aux backward is not built); call set_deterministic(False) or keep "
+            f"the {what} and alpha maps out of the loss")
+    if grad_out_color is None:  # (the native call takes H and W from it)
+        s, means3D = ctx.raster_settings, ctx.saved_tensors[0]
+        grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=means3D.dtype,
+                                     device=means3D.device)
+    if not aux:
+        return _RasterizeBase.native_backward(ctx, grad_out_color)
+    none = grad_out_color.new_empty(0)
+    return _RasterizeBase.native_backward(
+        ctx, grad_out_color, (none if grad_depth is None else grad_depth,
+                              none if grad_alpha is None else grad_alpha), inverse=inverse)
+
+
 class _RasterizeGaussiansAux(_RasterizeBase):
     """_RasterizeGaussians with the depth and alpha maps as two more
     differentiable outputs.  A backward that got neither map's cotangent is
@@ -205,32 +256,27 @@ class _RasterizeGaussiansAux(_RasterizeBase):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
-        color, depth, alpha, radii = _RasterizeBase.native_forward(
-            ctx, _C.rasterize_gaussians_aux, means3D, sh, colors_precomp, opacities, scales, rotations,
-            cov3Ds_precomp, raster_settings)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, alpha
+        return _maps_forward(ctx, _C.rasterize_gaussians_aux, means3D, sh, colors_precomp, opacities, scales,
+                             rotations, cov3Ds_precomp, raster_settings)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
-        if grad_out_color is None and grad_depth is None and grad_alpha is None:
-            return (None,) * 9
-        aux = grad_depth is not None or grad_alpha is not None
-        if aux and deterministic_requested():
-            raise RuntimeError(
-                "rasterize_gaussians_aux: the deterministic backward has no form that takes depth / alpha "
-                "cotangents (a deterministic aux backward is not built); call set_deterministic(False) or keep "
-                "the depth and alpha maps out of the loss")
-        if grad_out_color is None:  # (the native call takes H and W from it)
-            s, means3D = ctx.raster_settings, ctx.saved_tensors[0]
-            grad_out_color = torch.zeros((3, s.image_height, s.image_width), dtype=means3D.dtype,
-                                         device=means3D.device)
-        if not aux:
-            return _RasterizeBase.native_backward(ctx, grad_out_color)
-        none = grad_out_color.new_empty(0)
-        return _RasterizeBase.native_backward(
-            ctx, grad_out_color, (none if grad_depth is None else grad_depth,
-                                  none if grad_alpha is None else grad_alpha))
+        return _maps_backward(ctx, grad_out_color, grad_depth, grad_alpha, inverse=False)
+
+
+class _RasterizeGaussiansInvDepth(_RasterizeBase):
+    """_RasterizeGaussiansAux on the inverse-depth map ``sum (1 / z) alpha T``:
+    the same rules for absent cotangents and under the deterministic mode."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings):
+        return _maps_forward(ctx, _C.rasterize_gaussians_invdepth, means3D, sh, colors_precomp, opacities, scales,
+                             rotations, cov3Ds_precomp, raster_settings)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, grad_invdepth, grad_alpha):
+        return _maps_backward(ctx, grad_out_color, grad_invdepth, grad_alpha, inverse=True)
 
 
 class _ReferenceSettings(NamedTuple):
@@ -314,10 +360,15 @@ class GaussianRasterizer(nn.Module):
         return visible
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_aux=False):
+                cov3D_precomp=None, return_aux=False, return_invdepth=False):
         """The reference's ``(color, radii)``; with ``return_aux=True`` (an
-        extension) ``(color, radii, depth, alpha)`` -- rasterize_gaussians_aux."""
+        extension) ``(color, radii, depth, alpha)`` -- rasterize_gaussians_aux;
+        with ``return_invdepth=True`` (an extension) ``(color, radii, invdepth,
+        alpha)`` -- rasterize_gaussians_invdepth.  Not both."""
+        if return_aux and return_invdepth:
+            raise ValueError("GaussianRasterizer: return_aux and return_invdepth are two different calls; give one")
         _check_exactly_one(shs, colors_precomp, scales, rotations, cov3D_precomp)
-        fn = rasterize_gaussians_aux if return_aux else rasterize_gaussians
+        fn = (rasterize_gaussians_invdepth if return_invdepth else
+              rasterize_gaussians_aux if return_aux else rasterize_gaussians)
         return fn(means3D, means2D, _or_empty(shs), _or_empty(colors_precomp), opacities, _or_empty(scales),
                   _or_empty(rotations), _or_empty(cov3D_precomp), self.raster_settings)

@@ -57,18 +57,24 @@ def _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_c
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           starter=None, ender=None, return_aux=False):
+           starter=None, ender=None, return_aux=False, return_invdepth=False):
     """gaussian_renderer/__init__.py:18-113.  ``return_aux=True`` (an
     extension) adds ``"depth"`` and ``"alpha"``: the differentiable [1, H, W]
     maps of ``rasterization.rasterize_gaussians_aux`` (depth not normalised).
+    ``return_invdepth=True`` (an extension; not together with ``return_aux``)
+    adds ``"invdepth"`` and ``"alpha"``: the maps of
+    ``rasterization.rasterize_gaussians_invdepth``, ``invdepth = sum (1 / z)
+    alpha T`` -- the upstream renderer's ``"depth"`` output; the key ``"depth"``
+    stays ``sum z alpha T`` here.
     ``pipe.antialiasing`` (optional, default off) turns the Mip-Splatting 2D
     filter on (``GaussianRasterizationSettings.antialiasing``)."""
     pts, st, op = _operands(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color)
     rasterizer = GaussianRasterizer(raster_settings=st)
     if starter is not None:
         starter.record()
-    if return_aux:
-        image, radii, depth, alpha = rasterizer(means2D=pts, return_aux=True, **op)
+    if return_aux or return_invdepth:  # (both: the rasterizer raises)
+        image, radii, depth, alpha = rasterizer(means2D=pts, return_aux=return_aux, return_invdepth=return_invdepth,
+                                                **op)
     else:
         image, radii = rasterizer(means2D=pts, **op)
     if ender is not None:
@@ -76,4 +82,6 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     out = {"render": image, "viewspace_points": pts, "visibility_filter": radii > 0, "radii": radii}
     if return_aux:
         out["depth"], out["alpha"] = depth, alpha
+    if return_invdepth:
+        out["invdepth"], out["alpha"] = depth, alpha
     return out

@@ -21,6 +21,10 @@ scene/gaussian_model.py:149-407, laid out for one MI355X:
   bias correction, and leaves every other parameter and moment untouched;
 * the densification statistics (train.py:111-113) are one HIP launch;
 * the loss is the fused L1 + D-SSIM kernel (losses.py, csrc/loss.hip);
+* with an inverse-depth target (upstream's depth regularisation) the forward
+  also renders the inverse-depth map, the depth term
+  depth_l1_weight(iteration) * mean|(invdepth - target) * mask| has a fused
+  kernel pair of its own, and one backward takes both cotangents;
 * densify_and_prune / reset_opacity (:210-404) are rare (every 100 / 3000
   iterations) index-heavy reshapes: torch gather/cat on the device, after
   which the flat buffers are rebuilt at the new size.  Their order of
@@ -43,7 +47,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _C
-from .losses import l1_ssim_loss_terms
+from .losses import depth_l1_loss_terms, l1_ssim_loss_terms
 from .rasterization import (GaussianRasterizationSettings, GaussianRasterizer, native_backward_args,
                             native_forward_args)
 
@@ -72,6 +76,8 @@ class OptimizationParams:
     densify_from_iter: int = 500
     densify_until_iter: int = 15_000
     densify_grad_threshold: float = 0.0002
+    depth_l1_weight_init: float = 1.0  # upstream's depth regularisation: the weight decays log-linearly
+    depth_l1_weight_final: float = 0.01  # from _init to _final over `iterations`
     optimizer_type: str = "default"  # upstream's --optimizer_type: "default" | "sparse_adam"
 
 
@@ -139,6 +145,8 @@ class FlatGaussianModel:
         self.xyz_scheduler_args = get_expon_lr_func(
             lr_init=o.position_lr_init * self.spatial_lr_scale, lr_final=o.position_lr_final * self.spatial_lr_scale,
             lr_delay_mult=o.position_lr_delay_mult, max_steps=o.position_lr_max_steps)
+        self.depth_l1_weight = get_expon_lr_func(o.depth_l1_weight_init, o.depth_l1_weight_final,
+                                                 max_steps=o.iterations)
         self.steps: Dict[str, int] = {g: 0 for g in GROUPS}
         self._layout(int(raw["xyz"].shape[0]), {g: raw[g].to(dev, torch.float32) for g in GROUPS}, moments=None)
 
@@ -357,29 +365,42 @@ class FlatGaussianModel:
         self.has_grad["opacity"] = False
 
     # -------------------------------------------------------- rendering ---
-    def render(self, settings: GaussianRasterizationSettings):
+    def render(self, settings: GaussianRasterizationSettings, return_invdepth: bool = False):
         """gaussian_renderer/__init__.py:18-114 (default pipe: SH and the 3D
-        covariance evaluated by the rasterizer)."""
+        covariance evaluated by the rasterizer).  return_invdepth: also the
+        inverse-depth and alpha maps, as "invdepth" and "alpha"."""
         self._fresh_grads()
         screenspace_points = torch.zeros_like(self.param["xyz"], requires_grad=True) + 0
         screenspace_points.retain_grad()
         s = settings._replace(sh_degree=self.active_sh_degree)
-        image, radii = GaussianRasterizer(s)(
+        image, radii, *maps = GaussianRasterizer(s)(
             means3D=self.get_xyz, means2D=screenspace_points, shs=self.get_features, opacities=self.get_opacity,
-            scales=self.get_scaling, rotations=self.get_rotation)
-        return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
-                "radii": radii}
+            scales=self.get_scaling, rotations=self.get_rotation, return_invdepth=return_invdepth)
+        pkg = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+               "radii": radii}
+        if return_invdepth:
+            pkg["invdepth"], pkg["alpha"] = maps
+        return pkg
 
 
     def render_and_backward(self, settings: GaussianRasterizationSettings, gt_image: torch.Tensor,
-                            lambda_dssim: float, accumulate: bool = False):
+                            lambda_dssim: float, accumulate: bool = False, invdepth_target=None, depth_mask=None,
+                            depth_l1_weight: float = 1.0):
         """render -> L1 + D-SSIM -> backward without autograd: the activation
         kernel fills the rasterizer inputs from the raw segments, the fused
         loss kernel hands dL/dimage straight to the rasterizer backward, and
         the activation backward writes the raw-parameter gradients into the
         flat gradient buffer (gaussian_renderer/__init__.py:18-114 +
         train.py:89-93 + loss.backward()).  Same results as render() +
-        l1_ssim_loss + autograd (tests/test_gpu_training.py)."""
+        l1_ssim_loss + autograd (tests/test_gpu_training.py).
+
+        With ``invdepth_target`` ([1, H, W] or [H, W]; ``depth_mask`` alike or
+        None: ones) and a non-zero ``depth_l1_weight`` the forward is the
+        inverse-depth one, the depth term depth_l1_weight * mean|(invdepth -
+        target) * mask| joins the loss and the one backward takes both
+        cotangents; the terms gain "depth_l1", the unweighted term.  Without
+        a target, or at weight 0, every call made is the plain sequence's."""
+        depth = invdepth_target is not None and float(depth_l1_weight) != 0.0
         if accumulate:
             self._fresh_grads()
         s = settings._replace(sh_degree=self.active_sh_degree)
@@ -390,11 +411,21 @@ class FlatGaussianModel:
         e = torch.empty(0, device=self.device)
         xyz = raw["xyz"]
         operands = (xyz, a["shs"], e, a["opacities"], a["scales"], a["rotations"], e)
-        num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(*native_forward_args(s, *operands))
-        out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
-        (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = \
-            _C.rasterize_gaussians_backward_lean(*native_backward_args(
-                s, *operands, radii, geom, binning, img, num_rendered, d_image))
+        if depth:
+            num_rendered, color, invdepth, _alpha, radii, geom, binning, img = _C.rasterize_gaussians_invdepth(
+                *native_forward_args(s, *operands))
+            out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
+            out1, d_invdepth = _C.depth_l1_loss(invdepth, invdepth_target, depth_mask, float(depth_l1_weight))
+            (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = \
+                _C.rasterize_gaussians_backward_invdepth_lean(*native_backward_args(
+                    s, *operands, radii, geom, binning, img, num_rendered, d_image, (d_invdepth, e)))
+        else:
+            num_rendered, color, radii, geom, binning, img = _C.rasterize_gaussians(
+                *native_forward_args(s, *operands))
+            out3, d_image = _C.l1_ssim_loss(color, gt_image, float(lambda_dssim))
+            (d_means2D, _d_colors, d_opac, d_means3D, _d_cov3D, d_shs, d_scales, d_rot) = \
+                _C.rasterize_gaussians_backward_lean(*native_backward_args(
+                    s, *operands, radii, geom, binning, img, num_rendered, d_image))
         gv = {g: self.group_view(self.grads, g) for g in GROUPS}
         _C.activation_backward(d_shs, d_opac, d_scales, d_rot, d_means3D, raw["opacity"], raw["scaling"],
                                raw["rotation"], gv["xyz"], gv["f_dc"], gv["f_rest"], gv["opacity"], gv["scaling"],
@@ -402,20 +433,28 @@ class FlatGaussianModel:
         self._grads_stale = False
         self.mark_backward()
         pkg = {"render": color, "viewspace_grad": d_means2D, "visibility_filter": radii > 0, "radii": radii}
+        if depth:
+            pkg["invdepth"] = invdepth
+            return pkg, {"loss": out3[0] + float(depth_l1_weight) * out1[0], "l1": out3[1], "ssim": out3[2],
+                         "depth_l1": out1[0]}
         return pkg, {"loss": out3[0], "l1": out3[1], "ssim": out3[2]}
 
 
 def render_and_backward_views(model: FlatGaussianModel, settings: GaussianRasterizationSettings,
-                              gt_image: torch.Tensor, lambda_dssim: float, stats: bool, group=None):
+                              gt_image: torch.Tensor, lambda_dssim: float, stats: bool, group=None,
+                              invdepth_target=None):
     """The data-parallel fused iteration with the "views" exchange
     (data_parallel.py): activate -> forward -> fused loss -> blend backward
     of this rank's view -> all-gather of the view records -> multi-view
     parameter backward (the sum over all ranks' views, identical on every
     rank) -> activation backward into the flat gradient buffer.  With stats
     the densification statistics of every rank's view are accumulated too
-    (train.py:111-113), so no statistics all-reduce is needed afterwards."""
+    (train.py:111-113), so no statistics all-reduce is needed afterwards.
+    The view records carry no depth gradient: an ``invdepth_target`` with more
+    than one rank raises (data_parallel.refuse_depth_target)."""
     from . import data_parallel as DP
     DP.refuse_antialiasing(settings, "render_and_backward_views")
+    DP.refuse_depth_target(invdepth_target, "render_and_backward_views", group)
     s = settings._replace(sh_degree=model.active_sh_degree)
     raw = {g: model.group_view(model.params, g) for g in GROUPS}
     a = model._act
@@ -477,7 +516,8 @@ def reduce_visibility(radii: torch.Tensor, group=None) -> torch.Tensor:
 
 
 def forward_backward(model: FlatGaussianModel, iteration: int, settings: GaussianRasterizationSettings,
-                     gt_image: torch.Tensor, group=None, fused: bool = True, exchange: str = "views"):
+                     gt_image: torch.Tensor, group=None, fused: bool = True, exchange: str = "views",
+                     invdepth_target=None, depth_mask=None):
     """train.py:76-93 + the backward: learning-rate schedule, SH degree step,
     render, fused L1 + D-SSIM loss, backward into the flat gradient buffer,
     all-reduce over the data-parallel ranks.  fused=True runs the
@@ -486,15 +526,43 @@ def forward_backward(model: FlatGaussianModel, iteration: int, settings: Gaussia
     rasterizer + autograd).  Returns (render package, loss terms as device
     tensors); pkg["viewspace_grad"] is dL/dmeans2D.  With more than one rank
     and exchange="views" (fused only) the ranks exchange view records instead
-    of all-reducing the gradients (data_parallel.py)."""
+    of all-reducing the gradients (data_parallel.py).
+
+    invdepth_target ([1, H, W] or [H, W]; None: this view has no reliable
+    depth, upstream's depth_reliable) adds upstream's depth regularisation:
+    model.depth_l1_weight(iteration) * mean|(invdepth - target) * depth_mask|
+    (depth_mask None: ones), with the unweighted term as terms["depth_l1"].
+    Without a target, or at weight 0, the iteration is the plain one.  The
+    view exchange carries no depth gradient: with a target and more than one
+    rank it raises.  It raises on the ranks that were given a target only,
+    before the collective the others then wait in, and a per-camera None is
+    the normal case -- so a run that may pass a target on any rank chooses
+    exchange="params" for the whole run, not per iteration."""
     model.update_learning_rate(iteration)
     if iteration % 1000 == 0:
         model.oneupSHdegree()
+    depth_w = float(model.depth_l1_weight(iteration)) if invdepth_target is not None else 0.0
+    if depth_w == 0.0:
+        invdepth_target = depth_mask = None
     if fused and exchange == "views" and _world(group) > 1:
         return render_and_backward_views(model, settings, gt_image, model.opt.lambda_dssim,
-                                         stats=iteration < model.opt.densify_until_iter, group=group)
-    if fused:
+                                         stats=iteration < model.opt.densify_until_iter, group=group,
+                                         invdepth_target=invdepth_target)
+    if fused and invdepth_target is not None:
+        pkg, terms = model.render_and_backward(settings, gt_image, model.opt.lambda_dssim,
+                                               invdepth_target=invdepth_target, depth_mask=depth_mask,
+                                               depth_l1_weight=depth_w)
+    elif fused:
         pkg, terms = model.render_and_backward(settings, gt_image, model.opt.lambda_dssim)
+    elif invdepth_target is not None:
+        pkg = model.render(settings, return_invdepth=True)
+        loss, l1, ssim = l1_ssim_loss_terms(pkg["render"], gt_image, model.opt.lambda_dssim)
+        depth_loss, depth_l1 = depth_l1_loss_terms(pkg["invdepth"], invdepth_target, depth_mask, depth_w)
+        loss = loss + depth_loss
+        loss.backward()
+        model.mark_backward()
+        pkg["viewspace_grad"] = pkg["viewspace_points"].grad
+        terms = {"loss": loss.detach(), "l1": l1, "ssim": ssim, "depth_l1": depth_l1}
     else:
         pkg = model.render(settings)
         loss, l1, ssim = l1_ssim_loss_terms(pkg["render"], gt_image, model.opt.lambda_dssim)
@@ -533,9 +601,12 @@ def post_backward(model: FlatGaussianModel, iteration: int, pkg, scene_extent: f
 
 def training_iteration(model: FlatGaussianModel, iteration: int, settings: GaussianRasterizationSettings,
                        gt_image: torch.Tensor, scene_extent: float, white_background: bool = False,
-                       group=None, fused: bool = True, exchange: str = "views") -> Dict[str, torch.Tensor]:
+                       group=None, fused: bool = True, exchange: str = "views", invdepth_target=None,
+                       depth_mask=None) -> Dict[str, torch.Tensor]:
     """One iteration of train.py:67-125 (minus logging / saving / the GUI).
-    Returns the loss terms as device tensors (no host sync)."""
-    pkg, terms = forward_backward(model, iteration, settings, gt_image, group, fused, exchange)
+    Returns the loss terms as device tensors (no host sync).  invdepth_target /
+    depth_mask: upstream's depth regularisation (forward_backward)."""
+    pkg, terms = forward_backward(model, iteration, settings, gt_image, group, fused, exchange,
+                                  invdepth_target=invdepth_target, depth_mask=depth_mask)
     post_backward(model, iteration, pkg, scene_extent, white_background, group, fused)
     return terms

@@ -182,6 +182,62 @@ int gs_rasterizer_backward_ex(int P, int D, int M, int R, const float* backgroun
                               float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int antialiasing,
                               int deterministic, char* scratch, size_t scratch_bytes, int debug, void* stream);
 
+/* Inverse-depth map (no reference counterpart; the upstream rasterizer's
+ * third output, which its trainer's depth regularisation reads).  Base
+ * rasterizer only; an addition at ABI version 7: no layout and no existing
+ * entry changed.
+ *
+ *   invdepth[pix] = sum_i f_i * alpha_i * T_i,   f_i = 1.0f / z_i
+ *
+ * over exactly the colour blend's contributors, z_i the view-space depth the
+ * forward stores (z_i > 0.2 for every visible Gaussian, so f_i < 5), the
+ * quotient one correctly rounded float division; no background term and no
+ * normalisation.  Nothing is divided for a Gaussian with radii == 0.
+ *
+ * gs_rasterizer_forward_invdepth takes gs_rasterizer_forward_ex's arguments
+ * with out_invdepth ([height][width], every pixel written) in out_depth's
+ * place; out_invdepth and out_alpha are both required.  The colour launches
+ * are gs_rasterizer_forward_ex's, so out_color, radii and the three buffers
+ * are its bits, and out_alpha is gs_rasterizer_forward_aux's.
+ *
+ * gs_rasterizer_backward_invdepth takes gs_rasterizer_backward_ex's arguments
+ * with dL_dinvdepth in dL_ddepth's place.  Each of the three cotangents may be
+ * NULL (zeros); with both map cotangents NULL the call IS the plain backward.
+ * Inverse depth and alpha are blended as two more channels with features
+ * (f_i, 1); the per-Gaussian sum dL/df_i takes float 9 of the grad_accum row,
+ * and dL_dmean3D also carries -f_i^2 * dL/df_i * (V[2], V[6], V[10]) of the
+ * flat viewmatrix.  Float atomics: deterministic != 0 with a map cotangent
+ * returns a negative value.  The antialiasing flag composes, as in the _ex
+ * entries.  The AMR rasterizer and the multi-view / view-record entries have
+ * no inverse-depth form.  Usage:
+ *
+ *   K = gs_rasterizer_forward_invdepth(geom, bin, img, P, D, M, bg, W, H, ...,
+ *                                      prefiltered, antialiasing, color, radii,
+ *                                      invdepth, alpha, 0, stream);
+ *   gs_rasterizer_backward_invdepth(P, D, M, K, bg, W, H, ..., geom_ptr,
+ *                                   bin_ptr, img_ptr, dL_dcolor_img,
+ *                                   dL_dinvdepth, dL_dalpha, dL_dmean2D, ...,
+ *                                   antialiasing, 0, NULL, 0, 0, stream); */
+int gs_rasterizer_forward_invdepth(gs_buffer geometry, gs_buffer binning, gs_buffer image, int P, int D, int M,
+                                   const float* background, int width, int height, const float* means3D,
+                                   const float* shs, const float* colors_precomp, const float* opacities,
+                                   const float* scales, float scale_modifier, const float* rotations,
+                                   const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                   const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                   int antialiasing, float* out_color, int* radii, float* out_invdepth,
+                                   float* out_alpha, int debug, void* stream);
+int gs_rasterizer_backward_invdepth(int P, int D, int M, int R, const float* background, int width, int height,
+                                    const float* means3D, const float* shs, const float* colors_precomp,
+                                    const float* opacities, const float* scales, float scale_modifier,
+                                    const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                    const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy,
+                                    const int* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                    const float* dL_dpix, const float* dL_dinvdepth, const float* dL_dalpha,
+                                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                    float* dL_drot, int antialiasing, int deterministic, char* scratch,
+                                    size_t scratch_bytes, int debug, void* stream);
+
 /* Data-parallel training (no reference counterpart: the
  * reference trains one view per step on one GPU, train.py:67-125).
  *
@@ -454,6 +510,19 @@ int gs_simple_knn(int P, const float* points, float* mean_dists, gs_buffer scrat
  * fixed-order reduction (deterministic); no host synchronisation. */
 int gs_l1_ssim_loss(const float* image, const float* gt, int C, int H, int W, float lambda_dssim, float* grad,
                     float* out3, gs_buffer workspace, void* stream);
+
+/* The depth-regularisation term of the upstream trainer (no reference
+ * counterpart; an addition at ABI version 7):
+ *   out1[0] = mean over H*W of |(invdepth - target) * mask|       (unweighted)
+ *   grad    = weight * sgn * mask / (H*W)                         ([H][W])
+ * invdepth, target, mask: [H][W] float32 (device); mask may be NULL (ones).
+ * sgn is +1 / -1 / 0 as invdepth >, <, == target, times the sign of mask --
+ * decided by comparisons, never from a rounded difference -- and the gradient
+ * is evaluated in float32 in the order written.  One elementwise pass plus a
+ * fixed-order float64 reduction (deterministic); no host synchronisation.
+ * workspace is sized through its callback (at most 8 KiB). */
+int gs_depth_l1_loss(const float* invdepth, const float* target, const float* mask, int H, int W, float weight,
+                     float* grad, float* out1, gs_buffer workspace, void* stream);
 
 /* One torch.optim.Adam step (scene/gaussian_model.py:154-163: per-group
  * learning rates, betas (0.9, 0.999), eps 1e-15) over a flat f32 buffer of n
